@@ -10,6 +10,12 @@ applied per second = N_workers * rows * cols / step_time.
 
 Launch: python bench.py --gpus N --steps K --warmup W
 (N>1 via torch.distributed.run; reads RANK/WORLD_SIZE/MASTER_* from env.)
+
+A plain run sets up, warms up, times the K steps and prints the result
+line. ``--dump-outputs DIR`` additionally writes what the last timed step
+returned (DIR/<name>.npy) so two builds can be compared output for output;
+``--full`` adds the diagnostic measurements that take runs of their own
+(the per-phase add/get/barrier split).
 """
 
 import argparse
@@ -35,8 +41,18 @@ def parse_args():
     p.add_argument("--cols", type=int, default=128)
     p.add_argument("--updater", type=str, default="sgd")
     p.add_argument("--phase-steps", dest="phase_steps", type=int, default=20,
-                   help="diagnostic per-phase (add/get/barrier) timing "
-                        "steps run AFTER the contract region; 0 disables")
+                   help="with --full: diagnostic per-phase (add/get/barrier) "
+                        "timing steps run AFTER the contract region; "
+                        "0 disables")
+    p.add_argument("--full", action="store_true",
+                   help="also run the diagnostics that take runs of their "
+                        "own (per-phase timing); a plain run only times "
+                        "the contract region")
+    p.add_argument("--dump-outputs", dest="dump_outputs", type=str,
+                   default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step returned as DIR/<name>.npy (float32; an array "
+                        "over 32 MiB is cut to a fixed seeded row sample)")
     p.add_argument("--gb", type=float, default=4.0,
                    help="sweep mode: aggregate buffer size in GiB")
     p.add_argument("--app", type=str, default="matrix",
@@ -55,7 +71,38 @@ def parse_args():
     p.add_argument("--dense", action="store_true",
                    help="logreg: dense data mode (reference sparse=false "
                         "— GEMMs on the matrix cores via rocBLAS)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.dump_outputs and args.app != "matrix":
+        p.error("--dump-outputs is implemented for the flagship "
+                "--app matrix run only")
+    return args
+
+
+DUMP_BUDGET_BYTES = 32 << 20   # all dumped arrays together (cap: 64 MB)
+DUMP_SAMPLE_SEED = 0xD0A7
+
+
+def dump_outputs(dirname, arrays):
+    """Write each named 2-D tensor as ``dirname/<name>.npy`` (float32, or
+    float64 for double tensors). The byte budget is split evenly; an
+    array over its share is reduced to a fixed, seeded sample of its rows
+    (sorted row order), identical from run to run and build to build."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for i, (name, t) in enumerate(sorted(arrays.items())):
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        rows = t.shape[0]
+        row_bytes = max(t[0].numel(), 1) * (8 if dt == torch.float64 else 4)
+        keep = share // row_bytes
+        if rows > keep:
+            g = torch.Generator(device="cpu").manual_seed(
+                DUMP_SAMPLE_SEED + i)
+            idx = torch.randperm(rows, generator=g)[:keep].sort().values
+            t = t.index_select(0, idx.to(t.device))
+        np.save(os.path.join(dirname, name + ".npy"),
+                t.to(device="cpu", dtype=dt).contiguous().numpy())
 
 
 def main():
@@ -122,12 +169,15 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     updates_per_sec = n * args.rows * args.cols / (elapsed / args.steps)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"get_out": out})
+
     # diagnostic per-phase breakdown AFTER the contract region (VERDICT
     # r1 #2: make the first 8-GPU run diagnosable — at N>1 add =
     # reduce-scatter + updater kernel, get = all-gather; a slow phase
     # points straight at the collective vs the kernel)
     phases = None
-    if args.phase_steps > 0:
+    if args.full and args.phase_steps > 0:
         def timed(fn):
             mv.barrier()
             if cuda:

@@ -199,7 +199,7 @@ def test_selftest_dispatcher_ws2(name, tmp_path):
 
 @pytest.mark.parametrize("appargs", [
     ["--rows", "4000", "--cols", "8", "--steps", "3", "--warmup", "1",
-     "--phase-steps", "2"],
+     "--full", "--phase-steps", "2"],
     ["--app", "logreg", "--steps", "2", "--warmup", "1"],
     ["--app", "wordembedding", "--steps", "2", "--warmup", "1",
      "--block-words", "2000", "--vocab", "200", "--dim", "16"],
@@ -231,3 +231,54 @@ def test_bench_rehearsal_ws2(appargs, tmp_path):
     assert rec["n_gpus"] == 2 and "value" in rec and "metric" in rec
     if "--app" not in appargs:
         assert "phases" in rec and rec["phases"], rec
+
+
+def _run_bench_cpu(extra):
+    import json as _json
+    env = dict(os.environ)
+    env["PYTHONPATH"] = REPO + ":" + env.get("PYTHONPATH", "")
+    env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = ""
+    r = subprocess.run(
+        [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1"]
+        + extra, capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-1500:])
+    return _json.loads(
+        [l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run only times the contract region (no per-phase runs) and
+    --dump-outputs writes the last timed step's Get result: identical from
+    run to run, and equal to init - (warmup + steps) * delta (SGD)."""
+    import numpy as np
+    import torch
+    rows, cols, steps, warmup = 300, 8, 3, 2
+    args = ["--rows", str(rows), "--cols", str(cols), "--steps", str(steps),
+            "--warmup", str(warmup)]
+    rec = _run_bench_cpu(args + ["--dump-outputs", str(tmp_path / "a")])
+    assert rec["steps"] == steps and rec["ms_per_step"] > 0
+    assert rec["phases"] is None
+    _run_bench_cpu(args + ["--dump-outputs", str(tmp_path / "b")])
+    a = np.load(tmp_path / "a" / "get_out.npy")
+    b = np.load(tmp_path / "b" / "get_out.npy")
+    assert a.dtype == np.float32 and a.shape == (rows, cols)
+    assert np.array_equal(a, b)
+    g = torch.Generator(device="cpu").manual_seed(0x5EED)   # table 0 init
+    init = torch.rand(rows, cols, generator=g) * 0.2 - 0.1
+    g = torch.Generator(device="cpu").manual_seed(1234)     # rank 0 delta
+    delta = (torch.rand(rows * cols, generator=g) * 1e-4).view(rows, cols)
+    want = init.double() - (steps + warmup) * delta.double()
+    # 5 fp32 subtractions of values < 0.11: error <= 5 * 2^-24 * 0.11
+    assert np.abs(a - want.numpy()).max() <= 5 * 2.0 ** -24 * 0.11
+
+
+def test_bench_dump_outputs_samples_large_output(tmp_path):
+    """An output over the 32 MiB dump budget is cut to a row sample."""
+    import numpy as np
+    _run_bench_cpu(["--rows", "20000", "--cols", "512", "--steps", "1",
+                    "--warmup", "0", "--dump-outputs", str(tmp_path)])
+    f = tmp_path / "get_out.npy"
+    a = np.load(f)
+    assert a.dtype == np.float32 and a.shape == ((32 << 20) // 2048, 512)
+    assert os.path.getsize(f) <= 64 * 1000 * 1000
+    assert np.isfinite(a).all() and np.abs(a).max() <= 0.1001

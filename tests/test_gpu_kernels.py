@@ -250,7 +250,7 @@ def test_fused_stateful_add_get(updater, extra):
     mv.shutdown()
 
 
-def test_array_fused_add_get():
+def test_array_fused_add_get(tmp_path):
     import multiverso_amd as mv
     mv.init()
     t = mv.ArrayTable(10_000, updater_type="sgd")
@@ -262,14 +262,12 @@ def test_array_fused_add_get():
     assert torch.allclose(t.shard, -delta, rtol=1e-6, atol=1e-7)
     # checkpoint after a deferred add must flush first
     t.add(delta)
-    import tempfile, os
-    p = os.path.join(tempfile.gettempdir(), "arr_fused.bin")
+    p = str(tmp_path / "arr_fused.bin")
     t.store(p)
     t2 = mv.ArrayTable(10_000, updater_type="sgd")
     t2.load(p)
     torch.cuda.synchronize()
     assert torch.allclose(t2.get(), -2 * delta, rtol=1e-5, atol=1e-6)
-    os.remove(p)
     mv.shutdown()
 
 

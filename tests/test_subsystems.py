@@ -147,12 +147,12 @@ def test_sparse_matrix_dist():
     run_dist(_sparse_matrix_dist, 2)
 
 
-def _checkpoint_dist(rank, world):
+def _checkpoint_dist(rank, world, tmpdir):
     import multiverso_amd as mv
     import torch
-    import tempfile, os
+    import os
     mv.init(sync=True)
-    d = os.path.join(tempfile.gettempdir(), "mv_ckpt_test")
+    d = os.path.join(tmpdir, "mv_ckpt_test")
     a = mv.ArrayTable(10)
     a.add(torch.ones(10))
     mv.checkpoint(d)
@@ -165,8 +165,9 @@ def _checkpoint_dist(rank, world):
     mv.shutdown()
 
 
-def test_checkpoint_dist():
-    run_dist(_checkpoint_dist, 2)
+def test_checkpoint_dist(tmp_path):
+    import functools
+    run_dist(functools.partial(_checkpoint_dist, tmpdir=str(tmp_path)), 2)
 
 
 def _streaming_checkpoint(rank, world, tmpdir):
