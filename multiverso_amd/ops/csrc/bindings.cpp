@@ -10,27 +10,28 @@
 #include <cstdint>
 
 extern "C" {
+// elementwise updaters: a non-null `out` (the float* before the scalars)
+// selects the fused Add+Get form
 void mv_launch_copy(float*, const float*, int64_t, hipStream_t);
 void mv_launch_add(float*, const float*, int64_t, hipStream_t);
-void mv_launch_sgd(float*, const float*, int64_t, hipStream_t);
-void mv_launch_momentum(float*, float*, const float*, float, int64_t, hipStream_t);
-void mv_launch_adagrad(float*, float*, const float*, float, float, float,
-                       int64_t, hipStream_t);
-void mv_launch_sgd_copy(float*, const float*, float*, float, int64_t,
+void mv_launch_add_f64(double*, const double*, int64_t, hipStream_t);
+void mv_launch_add_i32(int32_t*, const int32_t*, int64_t, hipStream_t);
+void mv_launch_add_i64(int64_t*, const int64_t*, int64_t, hipStream_t);
+void mv_launch_sgd(float*, const float*, float*, float, int64_t, hipStream_t);
+void mv_launch_sgd_f64(double*, const double*, double*, double, int64_t,
+                       hipStream_t);
+void mv_launch_momentum(float*, float*, const float*, float*, float, int64_t,
                         hipStream_t);
-void mv_launch_momentum_copy(float*, float*, const float*, float*, float,
-                             int64_t, hipStream_t);
-void mv_launch_adagrad_copy(float*, float*, const float*, float*, float,
-                            float, float, int64_t, hipStream_t);
-void mv_launch_dcasgd_copy(float*, float*, const float*, float*, float,
-                           float, int64_t, hipStream_t);
-void mv_launch_dcasgda_copy(float*, float*, float*, const float*, float*,
-                            float, float, float, float, int64_t,
+void mv_launch_momentum_f64(double*, double*, const double*, double, int64_t,
                             hipStream_t);
-void mv_launch_dcasgd(float*, float*, const float*, float, float, int64_t,
-                      hipStream_t);
-void mv_launch_dcasgda(float*, float*, float*, const float*, float, float,
-                       float, float, int64_t, hipStream_t);
+void mv_launch_adagrad(float*, float*, const float*, float*, float, float,
+                       float, int64_t, hipStream_t);
+void mv_launch_adagrad_f64(double*, double*, const double*, double, double,
+                           double, int64_t, hipStream_t);
+void mv_launch_dcasgd(float*, float*, const float*, float*, float, float,
+                      int64_t, hipStream_t);
+void mv_launch_dcasgda(float*, float*, float*, const float*, float*, float,
+                       float, float, float, int64_t, hipStream_t);
 void mv_launch_row_gather(float*, const float*, const int64_t*, int64_t,
                           int64_t, hipStream_t);
 void mv_launch_row_scatter_add(float*, const float*, const int64_t*, float,
@@ -69,16 +70,6 @@ void mv_launch_lr_ftrl_fwd(const float*, const int64_t*, const float*,
 void mv_launch_lr_ftrl_scatter(float*, const int64_t*, const float*,
                                const int*, const float*, float, float,
                                float, float, int64_t, int64_t, hipStream_t);
-void mv_launch_add_f64(double*, const double*, int64_t, hipStream_t);
-void mv_launch_sgd_f64(double*, const double*, int64_t, hipStream_t);
-void mv_launch_momentum_f64(double*, double*, const double*, double, int64_t,
-                            hipStream_t);
-void mv_launch_adagrad_f64(double*, double*, const double*, double, double,
-                           double, int64_t, hipStream_t);
-void mv_launch_sgd_copy_f64(double*, const double*, double*, double, int64_t,
-                            hipStream_t);
-void mv_launch_add_i32(int32_t*, const int32_t*, int64_t, hipStream_t);
-void mv_launch_add_i64(int64_t*, const int64_t*, int64_t, hipStream_t);
 }
 
 namespace {
@@ -100,26 +91,39 @@ void check_dev(const torch::Tensor& t, const char* name,
   TORCH_CHECK(t.scalar_type() == st, name, " dtype mismatch");
 }
 
+// Validation shared by the elementwise wrappers: every tensor on the GPU,
+// contiguous and of dtype st (fp32, with check_f32's wording, when no st
+// is given), and all of one numel, which is returned.
+using Named = std::pair<const char*, torch::Tensor>;
+int64_t check_same(std::initializer_list<Named> ts,
+                   c10::optional<torch::ScalarType> st = c10::nullopt) {
+  for (const auto& t : ts) {
+    if (st) check_dev(t.second, t.first, *st);
+    else check_f32(t.second, t.first);
+  }
+  int64_t n = ts.begin()->second.numel();
+  for (const auto& t : ts)
+    TORCH_CHECK(t.second.numel() == n, "size mismatch");
+  return n;
+}
+
+float* f32(const torch::Tensor& t) { return t.data_ptr<float>(); }
+double* f64(const torch::Tensor& t) { return t.data_ptr<double>(); }
+
 void nt_copy(torch::Tensor dst, torch::Tensor src) {
-  check_f32(dst, "dst"); check_f32(src, "src");
-  TORCH_CHECK(dst.numel() == src.numel(), "size mismatch");
-  mv_launch_copy(dst.data_ptr<float>(), src.data_ptr<float>(), dst.numel(),
-                 cur_stream());
+  int64_t n = check_same({{"dst", dst}, {"src", src}});
+  mv_launch_copy(f32(dst), f32(src), n, cur_stream());
 }
 
 void add_inplace(torch::Tensor data, torch::Tensor delta) {
   // dtype-dispatched K1 (reference instantiates int/float/double tables,
   // array_table.cpp:153-154; int updater is add-only, updater.cpp:40-43)
   auto st = data.scalar_type();
-  check_dev(data, "data", st); check_dev(delta, "delta", st);
-  TORCH_CHECK(data.numel() == delta.numel(), "size mismatch");
-  int64_t n = data.numel();
+  int64_t n = check_same({{"data", data}, {"delta", delta}}, st);
   if (st == torch::kFloat32)
-    mv_launch_add(data.data_ptr<float>(), delta.data_ptr<float>(), n,
-                  cur_stream());
+    mv_launch_add(f32(data), f32(delta), n, cur_stream());
   else if (st == torch::kFloat64)
-    mv_launch_add_f64(data.data_ptr<double>(), delta.data_ptr<double>(), n,
-                      cur_stream());
+    mv_launch_add_f64(f64(data), f64(delta), n, cur_stream());
   else if (st == torch::kInt32)
     mv_launch_add_i32(data.data_ptr<int32_t>(), delta.data_ptr<int32_t>(), n,
                       cur_stream());
@@ -130,148 +134,113 @@ void add_inplace(torch::Tensor data, torch::Tensor delta) {
     TORCH_CHECK(false, "add_inplace: unsupported dtype ", data.dtype());
 }
 
-void sgd_update(torch::Tensor data, torch::Tensor delta) {
+// data += sign * delta; `out`, when given, also receives the updated data
+void launch_sgd(const char* fn, const torch::Tensor& data,
+                const torch::Tensor& delta, const torch::Tensor* out,
+                double sign, int64_t n) {
   auto st = data.scalar_type();
-  check_dev(data, "data", st); check_dev(delta, "delta", st);
-  TORCH_CHECK(data.numel() == delta.numel(), "size mismatch");
   if (st == torch::kFloat32)
-    mv_launch_sgd(data.data_ptr<float>(), delta.data_ptr<float>(),
-                  data.numel(), cur_stream());
+    mv_launch_sgd(f32(data), f32(delta), out ? f32(*out) : nullptr,
+                  (float)sign, n, cur_stream());
   else if (st == torch::kFloat64)
-    mv_launch_sgd_f64(data.data_ptr<double>(), delta.data_ptr<double>(),
-                      data.numel(), cur_stream());
+    mv_launch_sgd_f64(f64(data), f64(delta), out ? f64(*out) : nullptr, sign,
+                      n, cur_stream());
   else
-    TORCH_CHECK(false, "sgd_update: unsupported dtype ", data.dtype());
+    TORCH_CHECK(false, fn, ": unsupported dtype ", data.dtype());
+}
+
+void sgd_update(torch::Tensor data, torch::Tensor delta) {
+  int64_t n = check_same({{"data", data}, {"delta", delta}},
+                         data.scalar_type());
+  launch_sgd("sgd_update", data, delta, nullptr, -1.0, n);
+}
+
+void sgd_copy_update(torch::Tensor data, torch::Tensor delta,
+                     torch::Tensor out, double sign) {
+  int64_t n = check_same({{"data", data}, {"delta", delta}, {"out", out}},
+                         data.scalar_type());
+  launch_sgd("sgd_copy_update", data, delta, &out, sign, n);
 }
 
 void momentum_update(torch::Tensor data, torch::Tensor m, torch::Tensor delta,
                      double mu) {
   auto st = data.scalar_type();
-  check_dev(data, "data", st); check_dev(m, "m", st);
-  check_dev(delta, "delta", st);
-  TORCH_CHECK(data.numel() == delta.numel() && data.numel() == m.numel(),
-              "size mismatch");
+  int64_t n = check_same({{"data", data}, {"m", m}, {"delta", delta}}, st);
   if (st == torch::kFloat32)
-    mv_launch_momentum(data.data_ptr<float>(), m.data_ptr<float>(),
-                       delta.data_ptr<float>(), (float)mu, data.numel(),
+    mv_launch_momentum(f32(data), f32(m), f32(delta), nullptr, (float)mu, n,
                        cur_stream());
   else if (st == torch::kFloat64)
-    mv_launch_momentum_f64(data.data_ptr<double>(), m.data_ptr<double>(),
-                           delta.data_ptr<double>(), mu, data.numel(),
+    mv_launch_momentum_f64(f64(data), f64(m), f64(delta), mu, n,
                            cur_stream());
   else
     TORCH_CHECK(false, "momentum_update: unsupported dtype ", data.dtype());
 }
 
+void momentum_copy_update(torch::Tensor data, torch::Tensor m,
+                          torch::Tensor delta, torch::Tensor out, double mu) {
+  int64_t n = check_same({{"data", data}, {"m", m}, {"delta", delta},
+                          {"out", out}});
+  mv_launch_momentum(f32(data), f32(m), f32(delta), f32(out), (float)mu, n,
+                     cur_stream());
+}
+
 void adagrad_update(torch::Tensor data, torch::Tensor gsq, torch::Tensor delta,
                     double lr, double rho, double eps) {
   auto st = data.scalar_type();
-  check_dev(data, "data", st); check_dev(gsq, "gsq", st);
-  check_dev(delta, "delta", st);
-  TORCH_CHECK(data.numel() == delta.numel() && data.numel() == gsq.numel(),
-              "size mismatch");
+  int64_t n = check_same({{"data", data}, {"gsq", gsq}, {"delta", delta}}, st);
   if (st == torch::kFloat32)
-    mv_launch_adagrad(data.data_ptr<float>(), gsq.data_ptr<float>(),
-                      delta.data_ptr<float>(), (float)lr, (float)rho,
-                      (float)eps, data.numel(), cur_stream());
+    mv_launch_adagrad(f32(data), f32(gsq), f32(delta), nullptr, (float)lr,
+                      (float)rho, (float)eps, n, cur_stream());
   else if (st == torch::kFloat64)
-    mv_launch_adagrad_f64(data.data_ptr<double>(), gsq.data_ptr<double>(),
-                          delta.data_ptr<double>(), lr, rho, eps,
-                          data.numel(), cur_stream());
+    mv_launch_adagrad_f64(f64(data), f64(gsq), f64(delta), lr, rho, eps, n,
+                          cur_stream());
   else
     TORCH_CHECK(false, "adagrad_update: unsupported dtype ", data.dtype());
-}
-
-void sgd_copy_update(torch::Tensor data, torch::Tensor delta,
-                     torch::Tensor out, double sign) {
-  auto st = data.scalar_type();
-  check_dev(data, "data", st); check_dev(delta, "delta", st);
-  check_dev(out, "out", st);
-  TORCH_CHECK(data.numel() == delta.numel() && data.numel() == out.numel(),
-              "size mismatch");
-  if (st == torch::kFloat32)
-    mv_launch_sgd_copy(data.data_ptr<float>(), delta.data_ptr<float>(),
-                       out.data_ptr<float>(), (float)sign, data.numel(),
-                       cur_stream());
-  else if (st == torch::kFloat64)
-    mv_launch_sgd_copy_f64(data.data_ptr<double>(), delta.data_ptr<double>(),
-                           out.data_ptr<double>(), sign, data.numel(),
-                           cur_stream());
-  else
-    TORCH_CHECK(false, "sgd_copy_update: unsupported dtype ", data.dtype());
-}
-
-void momentum_copy_update(torch::Tensor data, torch::Tensor m,
-                          torch::Tensor delta, torch::Tensor out, double mu) {
-  check_f32(data, "data"); check_f32(m, "m"); check_f32(delta, "delta");
-  check_f32(out, "out");
-  TORCH_CHECK(data.numel() == delta.numel() && data.numel() == m.numel() &&
-              data.numel() == out.numel(), "size mismatch");
-  mv_launch_momentum_copy(data.data_ptr<float>(), m.data_ptr<float>(),
-                          delta.data_ptr<float>(), out.data_ptr<float>(),
-                          (float)mu, data.numel(), cur_stream());
 }
 
 void adagrad_copy_update(torch::Tensor data, torch::Tensor gsq,
                          torch::Tensor delta, torch::Tensor out,
                          double lr, double rho, double eps) {
-  check_f32(data, "data"); check_f32(gsq, "gsq"); check_f32(delta, "delta");
-  check_f32(out, "out");
-  TORCH_CHECK(data.numel() == delta.numel() && data.numel() == gsq.numel() &&
-              data.numel() == out.numel(), "size mismatch");
-  mv_launch_adagrad_copy(data.data_ptr<float>(), gsq.data_ptr<float>(),
-                         delta.data_ptr<float>(), out.data_ptr<float>(),
-                         (float)lr, (float)rho, (float)eps, data.numel(),
-                         cur_stream());
+  int64_t n = check_same({{"data", data}, {"gsq", gsq}, {"delta", delta},
+                          {"out", out}});
+  mv_launch_adagrad(f32(data), f32(gsq), f32(delta), f32(out), (float)lr,
+                    (float)rho, (float)eps, n, cur_stream());
+}
+
+void dcasgd_update(torch::Tensor data, torch::Tensor bak, torch::Tensor delta,
+                   double lr, double lambda) {
+  int64_t n = check_same({{"data", data}, {"bak", bak}, {"delta", delta}});
+  mv_launch_dcasgd(f32(data), f32(bak), f32(delta), nullptr, (float)lr,
+                   (float)lambda, n, cur_stream());
 }
 
 void dcasgd_copy_update(torch::Tensor data, torch::Tensor bak,
                         torch::Tensor delta, torch::Tensor out,
                         double lr, double lambda) {
-  check_f32(data, "data"); check_f32(bak, "bak"); check_f32(delta, "delta");
-  check_f32(out, "out");
-  TORCH_CHECK(data.numel() == delta.numel() && data.numel() == bak.numel() &&
-              data.numel() == out.numel(), "size mismatch");
-  mv_launch_dcasgd_copy(data.data_ptr<float>(), bak.data_ptr<float>(),
-                        delta.data_ptr<float>(), out.data_ptr<float>(),
-                        (float)lr, (float)lambda, data.numel(), cur_stream());
+  int64_t n = check_same({{"data", data}, {"bak", bak}, {"delta", delta},
+                          {"out", out}});
+  mv_launch_dcasgd(f32(data), f32(bak), f32(delta), f32(out), (float)lr,
+                   (float)lambda, n, cur_stream());
+}
+
+void dcasgda_update(torch::Tensor data, torch::Tensor bak, torch::Tensor msq,
+                    torch::Tensor delta, double lr, double lambda, double rho,
+                    double eps) {
+  int64_t n = check_same({{"data", data}, {"bak", bak}, {"msq", msq},
+                          {"delta", delta}});
+  mv_launch_dcasgda(f32(data), f32(bak), f32(msq), f32(delta), nullptr,
+                    (float)lr, (float)lambda, (float)rho, (float)eps, n,
+                    cur_stream());
 }
 
 void dcasgda_copy_update(torch::Tensor data, torch::Tensor bak,
                          torch::Tensor msq, torch::Tensor delta,
                          torch::Tensor out, double lr, double lambda,
                          double rho, double eps) {
-  check_f32(data, "data"); check_f32(bak, "bak"); check_f32(msq, "msq");
-  check_f32(delta, "delta"); check_f32(out, "out");
-  TORCH_CHECK(data.numel() == delta.numel() && data.numel() == bak.numel() &&
-              data.numel() == msq.numel() && data.numel() == out.numel(),
-              "size mismatch");
-  mv_launch_dcasgda_copy(data.data_ptr<float>(), bak.data_ptr<float>(),
-                         msq.data_ptr<float>(), delta.data_ptr<float>(),
-                         out.data_ptr<float>(), (float)lr, (float)lambda,
-                         (float)rho, (float)eps, data.numel(), cur_stream());
-}
-
-void dcasgd_update(torch::Tensor data, torch::Tensor bak, torch::Tensor delta,
-                   double lr, double lambda) {
-  check_f32(data, "data"); check_f32(bak, "bak"); check_f32(delta, "delta");
-  TORCH_CHECK(data.numel() == delta.numel() && data.numel() == bak.numel(),
-              "size mismatch");
-  mv_launch_dcasgd(data.data_ptr<float>(), bak.data_ptr<float>(),
-                   delta.data_ptr<float>(), (float)lr, (float)lambda,
-                   data.numel(), cur_stream());
-}
-
-void dcasgda_update(torch::Tensor data, torch::Tensor bak, torch::Tensor msq,
-                    torch::Tensor delta, double lr, double lambda, double rho,
-                    double eps) {
-  check_f32(data, "data"); check_f32(bak, "bak"); check_f32(msq, "msq");
-  check_f32(delta, "delta");
-  TORCH_CHECK(data.numel() == delta.numel() && data.numel() == bak.numel() &&
-              data.numel() == msq.numel(), "size mismatch");
-  mv_launch_dcasgda(data.data_ptr<float>(), bak.data_ptr<float>(),
-                    msq.data_ptr<float>(), delta.data_ptr<float>(), (float)lr,
-                    (float)lambda, (float)rho, (float)eps, data.numel(),
+  int64_t n = check_same({{"data", data}, {"bak", bak}, {"msq", msq},
+                          {"delta", delta}, {"out", out}});
+  mv_launch_dcasgda(f32(data), f32(bak), f32(msq), f32(delta), f32(out),
+                    (float)lr, (float)lambda, (float)rho, (float)eps, n,
                     cur_stream());
 }
 

@@ -8,11 +8,16 @@
 //
 // Design (per the CDNA4 HIP guide): every kernel here is memory-bound, so
 // the shape is {block = 256 threads (4 waves of 64), float4 16B/lane
-// vectorized loads/stores, grid-stride with the grid capped at 2048 blocks
-// (256 CUs x 8 blocks)}. The stateful updaters (momentum/adagrad) fuse the
-// state read-modify-write into the same pass as the weight update — one
-// trip through HBM3E instead of the 3-4 separate passes a torch-op
-// composition would make.
+// vectorized loads/stores, grid-stride}. The grid cap is probe-swept per
+// stream count (defines below): UPD_GRID = 768 blocks for add/sgd,
+// STATE_GRID = 768 for the stateful updaters, ELEM_GRID = 1024 for the
+// plain copy and the f64/int forms, COPY_BLOCK = 1024 threads x
+// COPY_GRID = 768 blocks for the fused Add+Get bodies; MAX_GRID = 2048
+// (256 CUs x 8 blocks) only caps the row-keyed, word2vec and logreg
+// kernels. The stateful updaters (momentum/adagrad/dcasgd) fuse the state
+// read-modify-write into the same pass as the weight update — one trip
+// through HBM3E instead of the 3-4 separate passes a torch-op composition
+// would make.
 //
 // No CUDA compatibility paths: this file is HIP-only, compiled by hipcc
 // with --offload-arch=gfx950.
@@ -21,6 +26,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #define WAVE 64
 #define BLOCK 256
@@ -44,24 +50,45 @@
 #define COPY_BLOCK 1024
 #define COPY_GRID 768
 
-static inline int grid_copy(int64_t work_items) {
-  int64_t blocks = (work_items + COPY_BLOCK - 1) / COPY_BLOCK;
-  if (blocks > COPY_GRID) blocks = COPY_GRID;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
 typedef float v4f __attribute__((ext_vector_type(4)));
 
+// Streaming access helpers, overloaded so each updater body is written
+// once: the float4 forms are non-temporal, the scalar forms (fp32 tails,
+// double, int) are plain loads and stores.
 static __device__ __forceinline__ v4f ntload(const v4f* p) {
   return __builtin_nontemporal_load(p);
 }
 static __device__ __forceinline__ void ntstore(v4f* p, v4f v) {
   __builtin_nontemporal_store(v, p);
 }
+template <class T>
+static __device__ __forceinline__ T ntload(const T* p) { return *p; }
+template <class T>
+static __device__ __forceinline__ void ntstore(T* p, T v) { *p = v; }
 
-static inline int grid_for_cap(int64_t work_items, int cap) {
-  int64_t blocks = (work_items + BLOCK - 1) / BLOCK;
+static __device__ __forceinline__ float rsq(float x) {
+  return __frsqrt_rn(x);
+}
+static __device__ __forceinline__ v4f rsq(v4f x) {
+  v4f r;
+  r.x = __frsqrt_rn(x.x); r.y = __frsqrt_rn(x.y);
+  r.z = __frsqrt_rn(x.z); r.w = __frsqrt_rn(x.w);
+  return r;
+}
+
+// element i of a T array viewed as an array of V (V = T, or v4f over float)
+template <class V, class T>
+static __device__ __forceinline__ V ld(const T* p, int64_t i) {
+  return ntload((const V*)p + i);
+}
+template <class V, class T>
+static __device__ __forceinline__ void st(T* p, int64_t i, V v) {
+  ntstore((V*)p + i, v);
+}
+
+static inline int grid_for_cap(int64_t work_items, int cap,
+                               int block = BLOCK) {
+  int64_t blocks = (work_items + block - 1) / block;
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   return (int)blocks;
@@ -71,191 +98,75 @@ static inline int grid_for(int64_t work_items) {
 }
 
 // ---------------------------------------------------------------------------
-// Elementwise updaters (K1-K4). Vectorized body processes n4 float4 groups;
-// a scalar tail handles n % 4. All pointers are 16B-aligned (torch allocs).
+// Elementwise updaters (K1-K4 + DC-ASGD). One op struct per updater holds
+// its pointers and scalars; step<V>(i) applies the update to element i of
+// the arrays viewed as V and returns the new weight. fp32 runs V = v4f over
+// the n/4 body and V = float over the n%4 tail (all pointers are
+// 16B-aligned torch allocs); double (every updater the reference
+// instantiates, array_table.cpp:153-154) and int32/int64 (add-only,
+// updater.cpp:40-43) run the same ops with V = T, plain scalar access.
+// Every step issues all its loads before its first store: struct members
+// carry no __restrict__, so a load written after a store would wait for it.
 // ---------------------------------------------------------------------------
 
-__global__ void k_add_f4(v4f* __restrict__ data,
-                         const v4f* __restrict__ delta, int64_t n4) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    ntstore(&data[i], ntload(&data[i]) + ntload(&delta[i]));
+template <class T>
+struct AddOp {
+  using elem = T;
+  T* data; const T* delta;
+  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+    V v = ld<V>(data, i) + ld<V>(delta, i);
+    st(data, i, v);
+    return v;
   }
-}
+};
 
-__global__ void k_add_tail(float* __restrict__ data,
-                           const float* __restrict__ delta,
-                           int64_t start, int64_t n) {
-  int64_t i = start + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) data[i] += delta[i];
-}
-
-__global__ void k_sgd_f4(v4f* __restrict__ data,
-                         const v4f* __restrict__ delta, int64_t n4) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    ntstore(&data[i], ntload(&data[i]) - ntload(&delta[i]));
+// sign = -1 is sgd; the fused Add+Get passes +1 for the default (add)
+// updater.
+template <class T>
+struct SgdOp {
+  using elem = T;
+  T* data; const T* delta; T sign;
+  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+    V v = ld<V>(data, i) + sign * ld<V>(delta, i);
+    st(data, i, v);
+    return v;
   }
-}
+};
 
-__global__ void k_sgd_tail(float* __restrict__ data,
-                           const float* __restrict__ delta,
-                           int64_t start, int64_t n) {
-  int64_t i = start + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) data[i] -= delta[i];
-}
-
-__global__ void k_momentum_f4(v4f* __restrict__ data,
-                              v4f* __restrict__ m,
-                              const v4f* __restrict__ delta,
-                              float mu, int64_t n4) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  float om = 1.0f - mu;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    v4f mm = mu * ntload(&m[i]) + om * ntload(&delta[i]);
-    ntstore(&m[i], mm);
-    ntstore(&data[i], ntload(&data[i]) - mm);
+template <class T>
+struct MomentumOp {
+  using elem = T;
+  T* data; T* m; const T* delta; T mu;
+  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+    V d = ld<V>(data, i);
+    // explicit fma, so that every instantiation rounds alike: left to
+    // contract on its own, the compiler fused mu*m + (1-mu)*delta in the
+    // float4 bodies and the fused tail but not in the plain scalar tail
+    V mm = __builtin_elementwise_fma((V)mu, ld<V>(m, i),
+                                     ((T)1 - mu) * ld<V>(delta, i));
+    st(m, i, mm);
+    d -= mm;
+    st(data, i, d);
+    return d;
   }
-}
+};
 
-__global__ void k_momentum_tail(float* __restrict__ data, float* __restrict__ m,
-                                const float* __restrict__ delta,
-                                float mu, int64_t start, int64_t n) {
-  int64_t i = start + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    float mm = mu * m[i] + (1.0f - mu) * delta[i];
-    m[i] = mm;
-    data[i] -= mm;
-  }
-}
-
-__global__ void k_adagrad_f4(v4f* __restrict__ data,
-                             v4f* __restrict__ gsq,
-                             const v4f* __restrict__ delta,
-                             float inv_lr, float rho, float eps, int64_t n4) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    v4f d = ntload(&data[i]), G = ntload(&gsq[i]);
-    v4f g = ntload(&delta[i]) * inv_lr;
+template <class T>
+struct AdagradOp {
+  using elem = T;
+  T* data; T* gsq; const T* delta; T inv_lr, rho, eps;
+  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+    V d = ld<V>(data, i), G = ld<V>(gsq, i);
+    V g = ld<V>(delta, i) * inv_lr;
     G += g * g;
-    d.x -= rho * g.x * __frsqrt_rn(G.x + eps);
-    d.y -= rho * g.y * __frsqrt_rn(G.y + eps);
-    d.z -= rho * g.z * __frsqrt_rn(G.z + eps);
-    d.w -= rho * g.w * __frsqrt_rn(G.w + eps);
-    ntstore(&gsq[i], G); ntstore(&data[i], d);
+    // double keeps the exact divide; fp32 uses the hardware rsq
+    if constexpr (std::is_same<T, double>::value) d -= rho * g / sqrt(G + eps);
+    else d -= rho * g * rsq(G + eps);
+    st(gsq, i, G);
+    st(data, i, d);
+    return d;
   }
-}
-
-__global__ void k_adagrad_tail(float* __restrict__ data, float* __restrict__ gsq,
-                               const float* __restrict__ delta,
-                               float inv_lr, float rho, float eps,
-                               int64_t start, int64_t n) {
-  int64_t i = start + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    float g = delta[i] * inv_lr;
-    float G = gsq[i] + g * g;
-    gsq[i] = G;
-    data[i] -= rho * g * __frsqrt_rn(G + eps);
-  }
-}
-
-// Fused Add+Get (single-rank fast path): an Add immediately followed by
-// a whole-table Get re-reads the shard the updater just wrote. Fusing
-// the Get's copy-out into the updater pass saves that re-read — 2.0 GB
-// instead of 2.5 GB per Add+Get step on the 1e6x128 headline config
-// (observable semantics identical: shard updated AND out filled with the
-// updated values).
-__global__ void k_sgd_copy_f4(v4f* __restrict__ data,
-                              const v4f* __restrict__ delta,
-                              v4f* __restrict__ out, float sign, int64_t n4) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    v4f v = ntload(&data[i]) + sign * ntload(&delta[i]);
-    ntstore(&data[i], v);
-    ntstore(&out[i], v);
-  }
-}
-
-__global__ void k_sgd_copy_tail(float* __restrict__ data,
-                                const float* __restrict__ delta,
-                                float* __restrict__ out, float sign,
-                                int64_t start, int64_t n) {
-  int64_t i = start + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    float v = data[i] + sign * delta[i];
-    data[i] = v;
-    out[i] = v;
-  }
-}
-
-// Fused stateful-updater + Get variants: same saving as k_sgd_copy for
-// momentum/adagrad/dcasgd(a) — the updated weights stream to the Get
-// buffer in the same pass instead of a separate shard re-read.
-__global__ void k_momentum_copy_f4(v4f* __restrict__ data, v4f* __restrict__ m,
-                                   const v4f* __restrict__ delta,
-                                   v4f* __restrict__ out, float mu, int64_t n4) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  float om = 1.0f - mu;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    v4f mm = mu * ntload(&m[i]) + om * ntload(&delta[i]);
-    ntstore(&m[i], mm);
-    v4f d = ntload(&data[i]) - mm;
-    ntstore(&data[i], d);
-    ntstore(&out[i], d);
-  }
-}
-
-__global__ void k_momentum_copy_tail(float* __restrict__ data,
-                                     float* __restrict__ m,
-                                     const float* __restrict__ delta,
-                                     float* __restrict__ out, float mu,
-                                     int64_t start, int64_t n) {
-  int64_t i = start + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    float mm = mu * m[i] + (1.0f - mu) * delta[i];
-    m[i] = mm;
-    float d = data[i] - mm;
-    data[i] = d;
-    out[i] = d;
-  }
-}
-
-__global__ void k_adagrad_copy_f4(v4f* __restrict__ data, v4f* __restrict__ gsq,
-                                  const v4f* __restrict__ delta,
-                                  v4f* __restrict__ out,
-                                  float inv_lr, float rho, float eps,
-                                  int64_t n4) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    v4f d = ntload(&data[i]), G = ntload(&gsq[i]);
-    v4f g = ntload(&delta[i]) * inv_lr;
-    G += g * g;
-    d.x -= rho * g.x * __frsqrt_rn(G.x + eps);
-    d.y -= rho * g.y * __frsqrt_rn(G.y + eps);
-    d.z -= rho * g.z * __frsqrt_rn(G.z + eps);
-    d.w -= rho * g.w * __frsqrt_rn(G.w + eps);
-    ntstore(&gsq[i], G);
-    ntstore(&data[i], d);
-    ntstore(&out[i], d);
-  }
-}
-
-__global__ void k_adagrad_copy_tail(float* __restrict__ data,
-                                    float* __restrict__ gsq,
-                                    const float* __restrict__ delta,
-                                    float* __restrict__ out,
-                                    float inv_lr, float rho, float eps,
-                                    int64_t start, int64_t n) {
-  int64_t i = start + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    float g = delta[i] * inv_lr;
-    float G = gsq[i] + g * g;
-    gsq[i] = G;
-    float d = data[i] - rho * g * __frsqrt_rn(G + eps);
-    data[i] = d;
-    out[i] = d;
-  }
-}
+};
 
 // DC-ASGD updaters ("dcasgd"/"dcasgda", selected at reference
 // updater.cpp:51-54 from a submodule ABSENT from the snapshot
@@ -268,161 +179,157 @@ __global__ void k_adagrad_copy_tail(float* __restrict__ data,
 //   bak   = w            (per-worker backup, updated after the step)
 // Adaptive variant keeps a mean-square m = rho*m + (1-rho)*g*g and uses
 // lambda / sqrt(m + eps) as the compensation coefficient.
-__global__ void k_dcasgd_f4(v4f* __restrict__ data, v4f* __restrict__ bak,
-                            const v4f* __restrict__ delta,
-                            float lr, float lambda, int64_t n4) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    v4f w = ntload(&data[i]), b = ntload(&bak[i]);
-    v4f g = ntload(&delta[i]);
+struct DcasgdOp {
+  using elem = float;
+  float* data; float* bak; const float* delta; float lr, lambda;
+  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+    V w = ld<V>(data, i), b = ld<V>(bak, i);
+    V g = ld<V>(delta, i);
     w -= lr * (g + lambda * g * g * (w - b));
-    ntstore(&data[i], w);
-    ntstore(&bak[i], w);
+    st(data, i, w);
+    st(bak, i, w);
+    return w;
   }
-}
+};
 
-__global__ void k_dcasgd_tail(float* __restrict__ data, float* __restrict__ bak,
-                              const float* __restrict__ delta,
-                              float lr, float lambda, int64_t start, int64_t n) {
-  int64_t i = start + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    float g = delta[i];
-    float w = data[i] - lr * (g + lambda * g * g * (data[i] - bak[i]));
-    data[i] = w;
-    bak[i] = w;
-  }
-}
-
-__global__ void k_dcasgda_f4(v4f* __restrict__ data, v4f* __restrict__ bak,
-                             v4f* __restrict__ msq,
-                             const v4f* __restrict__ delta,
-                             float lr, float lambda, float rho, float eps,
-                             int64_t n4) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  float om = 1.0f - rho;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    v4f w = ntload(&data[i]), b = ntload(&bak[i]);
-    v4f g = ntload(&delta[i]);
-    v4f m = rho * ntload(&msq[i]) + om * g * g;
-    ntstore(&msq[i], m);
-    v4f lam;
-    lam.x = lambda * __frsqrt_rn(m.x + eps);
-    lam.y = lambda * __frsqrt_rn(m.y + eps);
-    lam.z = lambda * __frsqrt_rn(m.z + eps);
-    lam.w = lambda * __frsqrt_rn(m.w + eps);
+struct DcasgdaOp {
+  using elem = float;
+  float* data; float* bak; float* msq; const float* delta;
+  float lr, lambda, rho, eps;
+  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+    V w = ld<V>(data, i), b = ld<V>(bak, i);
+    V g = ld<V>(delta, i);
+    V m = rho * ld<V>(msq, i) + (1.0f - rho) * g * g;
+    st(msq, i, m);
+    V lam = lambda * rsq(m + eps);
     w -= lr * (g + lam * g * g * (w - b));
-    ntstore(&data[i], w);
-    ntstore(&bak[i], w);
+    st(data, i, w);
+    st(bak, i, w);
+    return w;
   }
-}
+};
 
-__global__ void k_dcasgda_tail(float* __restrict__ data, float* __restrict__ bak,
-                               float* __restrict__ msq,
-                               const float* __restrict__ delta,
-                               float lr, float lambda, float rho, float eps,
-                               int64_t start, int64_t n) {
-  int64_t i = start + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    float g = delta[i];
-    float m = rho * msq[i] + (1.0f - rho) * g * g;
-    msq[i] = m;
-    float w = data[i]
-        - lr * (g + lambda * __frsqrt_rn(m + eps) * g * g * (data[i] - bak[i]));
-    data[i] = w;
-    bak[i] = w;
+// K7 Access / shard copy-out: non-temporal streaming copy.
+struct CopyOp {
+  using elem = float;
+  float* dst; const float* src;
+  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+    V v = ld<V>(src, i);
+    st(dst, i, v);
+    return v;
   }
-}
+};
 
-__global__ void k_dcasgd_copy_f4(v4f* __restrict__ data, v4f* __restrict__ bak,
-                                 const v4f* __restrict__ delta,
-                                 v4f* __restrict__ out,
-                                 float lr, float lambda, int64_t n4) {
+// The one elementwise kernel: grid-stride over V-elements [start, n).
+// COPY is the fused Add+Get (single-rank fast path): an Add immediately
+// followed by a whole-table Get re-reads the shard the updater just
+// wrote. Streaming the updated weights to the Get buffer in the same pass
+// saves that re-read — 2.0 GB instead of 2.5 GB per Add+Get step on the
+// 1e6x128 headline config (observable semantics identical: shard updated
+// AND out filled with the updated values).
+template <class Op, class V, bool COPY>
+__global__ void k_elem(Op op, V* __restrict__ out, int64_t start, int64_t n) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    v4f w = ntload(&data[i]), b = ntload(&bak[i]);
-    v4f g = ntload(&delta[i]);
-    w -= lr * (g + lambda * g * g * (w - b));
-    ntstore(&data[i], w);
-    ntstore(&bak[i], w);
-    ntstore(&out[i], w);
+  for (int64_t i = start + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < n; i += stride) {
+    V v = op.template step<V>(i);
+    if (COPY) ntstore(&out[i], v);
   }
 }
 
-__global__ void k_dcasgd_copy_tail(float* __restrict__ data,
-                                   float* __restrict__ bak,
-                                   const float* __restrict__ delta,
-                                   float* __restrict__ out,
-                                   float lr, float lambda,
-                                   int64_t start, int64_t n) {
-  int64_t i = start + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    float g = delta[i];
-    float w = data[i] - lr * (g + lambda * g * g * (data[i] - bak[i]));
-    data[i] = w;
-    bak[i] = w;
-    out[i] = w;
+// fp32: float4 body over n/4 vectors with the given grid cap and block,
+// then one wave over the n%4 scalar tail. Other types: scalar grid-stride.
+template <bool COPY, class Op>
+static void launch_elem(const Op& op, typename Op::elem* out, int64_t n,
+                        int cap, int block, hipStream_t s) {
+  using T = typename Op::elem;
+  if constexpr (std::is_same<T, float>::value) {
+    int64_t n4 = n / 4;
+    if (n4) k_elem<Op, v4f, COPY><<<grid_for_cap(n4, cap, block), block, 0,
+                                    s>>>(op, (v4f*)out, 0, n4);
+    if (n > n4 * 4) k_elem<Op, float, COPY><<<1, 64, 0, s>>>(op, out, n4 * 4,
+                                                             n);
+  } else if (n > 0) {
+    k_elem<Op, T, COPY><<<grid_for_cap(n, cap, block), block, 0, s>>>(
+        op, out, 0, n);
   }
 }
 
-__global__ void k_dcasgda_copy_f4(v4f* __restrict__ data, v4f* __restrict__ bak,
-                                  v4f* __restrict__ msq,
-                                  const v4f* __restrict__ delta,
-                                  v4f* __restrict__ out,
-                                  float lr, float lambda, float rho, float eps,
-                                  int64_t n4) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  float om = 1.0f - rho;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    v4f w = ntload(&data[i]), b = ntload(&bak[i]);
-    v4f g = ntload(&delta[i]);
-    v4f m = rho * ntload(&msq[i]) + om * g * g;
-    ntstore(&msq[i], m);
-    v4f lam;
-    lam.x = lambda * __frsqrt_rn(m.x + eps);
-    lam.y = lambda * __frsqrt_rn(m.y + eps);
-    lam.z = lambda * __frsqrt_rn(m.z + eps);
-    lam.w = lambda * __frsqrt_rn(m.w + eps);
-    w -= lr * (g + lam * g * g * (w - b));
-    ntstore(&data[i], w);
-    ntstore(&bak[i], w);
-    ntstore(&out[i], w);
-  }
+// fp32 updater launch: a non-null `out` selects the fused Add+Get form
+// with its fat-block geometry (COPY_BLOCK x COPY_GRID, see the sweep note
+// at the COPY_BLOCK define); otherwise BLOCK threads x `cap` blocks.
+template <class Op>
+static void launch_update(const Op& op, float* out, int64_t n, int cap,
+                          hipStream_t s) {
+  if (out) launch_elem<true>(op, out, n, COPY_GRID, COPY_BLOCK, s);
+  else launch_elem<false>(op, nullptr, n, cap, BLOCK, s);
 }
 
-__global__ void k_dcasgda_copy_tail(float* __restrict__ data,
-                                    float* __restrict__ bak,
-                                    float* __restrict__ msq,
-                                    const float* __restrict__ delta,
-                                    float* __restrict__ out,
-                                    float lr, float lambda, float rho,
-                                    float eps, int64_t start, int64_t n) {
-  int64_t i = start + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    float g = delta[i];
-    float m = rho * msq[i] + (1.0f - rho) * g * g;
-    msq[i] = m;
-    float w = data[i]
-        - lr * (g + lambda * __frsqrt_rn(m + eps) * g * g * (data[i] - bak[i]));
-    data[i] = w;
-    bak[i] = w;
-    out[i] = w;
-  }
+extern "C" {
+
+void mv_launch_copy(float* dst, const float* src, int64_t n, hipStream_t s) {
+  launch_elem<false>(CopyOp{dst, src}, nullptr, n, ELEM_GRID, BLOCK, s);
 }
 
-__global__ void k_copy_f4(v4f* __restrict__ dst,
-                          const v4f* __restrict__ src, int64_t n4) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    ntstore(&dst[i], ntload(&src[i]));
-  }
+void mv_launch_add(float* data, const float* delta, int64_t n, hipStream_t s) {
+  launch_elem<false>(AddOp<float>{data, delta}, nullptr, n, UPD_GRID, BLOCK, s);
+}
+void mv_launch_add_f64(double* d, const double* x, int64_t n, hipStream_t s) {
+  launch_elem<false>(AddOp<double>{d, x}, nullptr, n, ELEM_GRID, BLOCK, s);
+}
+void mv_launch_add_i32(int32_t* d, const int32_t* x, int64_t n, hipStream_t s) {
+  launch_elem<false>(AddOp<int32_t>{d, x}, nullptr, n, ELEM_GRID, BLOCK, s);
+}
+void mv_launch_add_i64(int64_t* d, const int64_t* x, int64_t n, hipStream_t s) {
+  launch_elem<false>(AddOp<int64_t>{d, x}, nullptr, n, ELEM_GRID, BLOCK, s);
 }
 
-__global__ void k_copy_tail(float* __restrict__ dst,
-                            const float* __restrict__ src,
-                            int64_t start, int64_t n) {
-  int64_t i = start + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = src[i];
+void mv_launch_sgd(float* data, const float* delta, float* out, float sign,
+                   int64_t n, hipStream_t s) {
+  launch_update(SgdOp<float>{data, delta, sign}, out, n, UPD_GRID, s);
 }
+void mv_launch_sgd_f64(double* d, const double* x, double* out, double sign,
+                       int64_t n, hipStream_t s) {
+  SgdOp<double> op{d, x, sign};
+  if (out) launch_elem<true>(op, out, n, STATE_GRID, BLOCK, s);
+  else launch_elem<false>(op, nullptr, n, ELEM_GRID, BLOCK, s);
+}
+
+void mv_launch_momentum(float* data, float* m, const float* delta, float* out,
+                        float mu, int64_t n, hipStream_t s) {
+  launch_update(MomentumOp<float>{data, m, delta, mu}, out, n, STATE_GRID, s);
+}
+void mv_launch_momentum_f64(double* d, double* m, const double* x, double mu,
+                            int64_t n, hipStream_t s) {
+  launch_elem<false>(MomentumOp<double>{d, m, x, mu}, nullptr, n, STATE_GRID,
+                     BLOCK, s);
+}
+
+void mv_launch_adagrad(float* data, float* gsq, const float* delta, float* out,
+                       float lr, float rho, float eps, int64_t n,
+                       hipStream_t s) {
+  launch_update(AdagradOp<float>{data, gsq, delta, 1.0f / lr, rho, eps}, out,
+                n, STATE_GRID, s);
+}
+void mv_launch_adagrad_f64(double* d, double* g, const double* x, double lr,
+                           double rho, double eps, int64_t n, hipStream_t s) {
+  launch_elem<false>(AdagradOp<double>{d, g, x, 1.0 / lr, rho, eps}, nullptr,
+                     n, STATE_GRID, BLOCK, s);
+}
+
+void mv_launch_dcasgd(float* data, float* bak, const float* delta, float* out,
+                      float lr, float lambda, int64_t n, hipStream_t s) {
+  launch_update(DcasgdOp{data, bak, delta, lr, lambda}, out, n, STATE_GRID, s);
+}
+
+void mv_launch_dcasgda(float* data, float* bak, float* msq, const float* delta,
+                       float* out, float lr, float lambda, float rho,
+                       float eps, int64_t n, hipStream_t s) {
+  launch_update(DcasgdaOp{data, bak, msq, delta, lr, lambda, rho, eps}, out,
+                n, STATE_GRID, s);
+}
+
+}  // extern "C"
 
 // ---------------------------------------------------------------------------
 // Row-keyed gather/scatter (K5/K6): shard is [local_rows, cols] row-major,
@@ -431,286 +338,99 @@ __global__ void k_copy_tail(float* __restrict__ dst,
 // the gather; the scatter uses device-scope atomicAdd so duplicate rows
 // (the same row touched by several workers in one exchange) accumulate
 // correctly.
+//
+// Idx is the loop-index type. A 64-bit divide is ~40 cycles per element
+// and these kernels run one divide per 4 B moved, so the launchers pick
+// Idx = uint32_t whenever the element count fits (all real pulls and
+// pushes do) and int64_t otherwise. Only the (i -> r, c) math narrows —
+// the shard offset stays 64-bit (1e9-row tables).
+//
+// ATOMIC = false are the unique-rows forms: when the caller guarantees no
+// duplicate row ids (e.g. a sorted-unique union pushed from ONE rank) the
+// atomics are unnecessary — plain read-modify-write is substantially
+// faster for scattered few-column rows.
 // ---------------------------------------------------------------------------
 
-__global__ void k_row_gather_f4(float4* __restrict__ out,
-                                const float4* __restrict__ shard,
-                                const int64_t* __restrict__ rows,
-                                int64_t nrows, int64_t cols4) {
-  int64_t total = nrows * cols4;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    int64_t r = i / cols4, c = i % cols4;
-    out[i] = shard[rows[r] * cols4 + c];
-  }
-}
-
-__global__ void k_row_gather_f4_u32(float4* __restrict__ out,
-                                    const float4* __restrict__ shard,
-                                    const int64_t* __restrict__ rows,
-                                    uint32_t total4, uint32_t cols4) {
-  uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total4;
-       i += stride) {
-    uint32_t r = i / cols4, c = i - r * cols4;
-    out[i] = shard[rows[r] * (int64_t)cols4 + c];
-  }
-}
-
-__global__ void k_row_gather(float* __restrict__ out,
-                             const float* __restrict__ shard,
+// V = float, float2 or float4 column groups; total and cols count V's.
+template <class V, class Idx>
+__global__ void k_row_gather(V* __restrict__ out, const V* __restrict__ shard,
                              const int64_t* __restrict__ rows,
-                             int64_t nrows, int64_t cols) {
-  int64_t total = nrows * cols;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    int64_t r = i / cols, c = i % cols;
-    out[i] = shard[rows[r] * cols + c];
-  }
-}
-
-// u32 loop-index variant: a 64-bit divide is ~40 cycles per element and
-// these gathers run one divide per 4 B moved.  Only the (i -> r, c)
-// math narrows — the shard offset stays 64-bit (1e9-row tables).
-// Launcher picks this whenever total fits u32 (all real pulls do).
-__global__ void k_row_gather_u32(float* __restrict__ out,
-                                 const float* __restrict__ shard,
-                                 const int64_t* __restrict__ rows,
-                                 uint32_t total, uint32_t cols) {
-  uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
+                             Idx total, Idx cols) {
+  Idx stride = (Idx)gridDim.x * blockDim.x;
+  for (Idx i = (Idx)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += stride) {
-    uint32_t r = i / cols, c = i - r * cols;
+    Idx r = i / cols, c = i - r * cols;
     out[i] = shard[rows[r] * (int64_t)cols + c];
   }
 }
 
-__global__ void k_row_gather_f2_u32(float2* __restrict__ out,
-                                    const float2* __restrict__ shard,
-                                    const int64_t* __restrict__ rows,
-                                    uint32_t total2, uint32_t cols2) {
-  uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total2;
-       i += stride) {
-    uint32_t r = i / cols2, c = i - r * cols2;
-    out[i] = shard[rows[r] * (int64_t)cols2 + c];
-  }
-}
-
+template <class Idx, bool ATOMIC>
 __global__ void k_row_scatter_add(float* __restrict__ shard,
                                   const float* __restrict__ vals,
                                   const int64_t* __restrict__ rows,
-                                  float sign, int64_t nrows, int64_t cols) {
-  int64_t total = nrows * cols;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    int64_t r = i / cols, c = i % cols;
-    atomicAdd(&shard[rows[r] * cols + c], sign * vals[i]);
+                                  float sign, Idx total, Idx cols) {
+  Idx stride = (Idx)gridDim.x * blockDim.x;
+  for (Idx i = (Idx)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += stride) {
+    Idx r = i / cols, c = i - r * cols;
+    int64_t k = rows[r] * (int64_t)cols + c;
+    if (ATOMIC) atomicAdd(&shard[k], sign * vals[i]);
+    else shard[k] += sign * vals[i];
   }
 }
 
-// unique-rows variants: when the caller guarantees no duplicate row ids
-// (e.g. a sorted-unique union pushed from ONE rank) the atomics are
-// unnecessary — plain read-modify-write is substantially faster for
-// scattered few-column rows.
-__global__ void k_row_scatter_add_u(float* __restrict__ shard,
-                                    const float* __restrict__ vals,
-                                    const int64_t* __restrict__ rows,
-                                    float sign, int64_t nrows, int64_t cols) {
-  int64_t total = nrows * cols;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    int64_t r = i / cols, c = i % cols;
-    int64_t k = rows[r] * cols + c;
-    shard[k] += sign * vals[i];
-  }
-}
-
-// u32 loop-index forms (see k_row_gather_u32: one 64-bit divide per 4 B
-// is real VALU time on a gather/scatter; the shard offset stays 64-bit)
-__global__ void k_row_scatter_add_u32(float* __restrict__ shard,
+// Keyed AdaGrad scatter-update (K15 + K4 keyed form): for each incoming
+// (row, value) pair apply the adagrad step to the owned shard row. Used by
+// the LogisticRegression sparse path (BASELINE config: 1e9 sparse
+// features, AdaGrad updater). Duplicate rows race benignly (hogwild):
+// G accumulates via atomicAdd; the weight step uses the post-add G.
+template <class Idx, bool ATOMIC>
+__global__ void k_row_scatter_adagrad(float* __restrict__ shard,
+                                      float* __restrict__ gsq,
                                       const float* __restrict__ vals,
                                       const int64_t* __restrict__ rows,
-                                      float sign, uint32_t total,
-                                      uint32_t cols) {
-  uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
+                                      float inv_lr, float rho, float eps,
+                                      Idx total, Idx cols) {
+  Idx stride = (Idx)gridDim.x * blockDim.x;
+  for (Idx i = (Idx)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += stride) {
-    uint32_t r = i / cols, c = i - r * cols;
-    atomicAdd(&shard[rows[r] * (int64_t)cols + c], sign * vals[i]);
-  }
-}
-
-__global__ void k_row_scatter_add_u_u32(float* __restrict__ shard,
-                                        const float* __restrict__ vals,
-                                        const int64_t* __restrict__ rows,
-                                        float sign, uint32_t total,
-                                        uint32_t cols) {
-  uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += stride) {
-    uint32_t r = i / cols, c = i - r * cols;
+    Idx r = i / cols, c = i - r * cols;
     int64_t k = rows[r] * (int64_t)cols + c;
-    shard[k] += sign * vals[i];
+    float g = vals[i] * inv_lr;
+    if (g != 0.0f) {
+      float G;
+      if (ATOMIC) G = atomicAdd(&gsq[k], g * g) + g * g;
+      else { G = gsq[k] + g * g; gsq[k] = G; }
+      float dw = -rho * g * rsq(G + eps);
+      if (ATOMIC) atomicAdd(&shard[k], dw);
+      else shard[k] += dw;
+    }
   }
 }
-
-// ---------------------------------------------------------------------------
-// extern "C" launchers
-// ---------------------------------------------------------------------------
 
 extern "C" {
-
-// K7 Access / shard copy-out: non-temporal streaming copy.
-void mv_launch_copy(float* dst, const float* src, int64_t n, hipStream_t s) {
-  int64_t n4 = n / 4;
-  if (n4) k_copy_f4<<<grid_for_cap(n4, ELEM_GRID), BLOCK, 0, s>>>(
-      (v4f*)dst, (const v4f*)src, n4);
-  int64_t tail = n - n4 * 4;
-  if (tail) k_copy_tail<<<1, 64, 0, s>>>(dst, src, n4 * 4, n);
-}
-
-void mv_launch_add(float* data, const float* delta, int64_t n, hipStream_t s) {
-  int64_t n4 = n / 4;
-  if (n4) k_add_f4<<<grid_for_cap(n4, UPD_GRID), BLOCK, 0, s>>>(
-      (v4f*)data, (const v4f*)delta, n4);
-  int64_t tail = n - n4 * 4;
-  if (tail) k_add_tail<<<1, 64, 0, s>>>(data, delta, n4 * 4, n);
-}
-
-void mv_launch_sgd(float* data, const float* delta, int64_t n, hipStream_t s) {
-  int64_t n4 = n / 4;
-  if (n4) k_sgd_f4<<<grid_for_cap(n4, UPD_GRID), BLOCK, 0, s>>>(
-      (v4f*)data, (const v4f*)delta, n4);
-  int64_t tail = n - n4 * 4;
-  if (tail) k_sgd_tail<<<1, 64, 0, s>>>(data, delta, n4 * 4, n);
-}
-
-void mv_launch_momentum(float* data, float* m, const float* delta, float mu,
-                        int64_t n, hipStream_t s) {
-  int64_t n4 = n / 4;
-  if (n4) k_momentum_f4<<<grid_for_cap(n4, STATE_GRID), BLOCK, 0, s>>>(
-      (v4f*)data, (v4f*)m, (const v4f*)delta, mu, n4);
-  int64_t tail = n - n4 * 4;
-  if (tail) k_momentum_tail<<<1, 64, 0, s>>>(data, m, delta, mu, n4 * 4, n);
-}
-
-void mv_launch_adagrad(float* data, float* gsq, const float* delta,
-                       float lr, float rho, float eps, int64_t n, hipStream_t s) {
-  float inv_lr = 1.0f / lr;
-  int64_t n4 = n / 4;
-  if (n4) k_adagrad_f4<<<grid_for_cap(n4, STATE_GRID), BLOCK, 0, s>>>(
-      (v4f*)data, (v4f*)gsq, (const v4f*)delta, inv_lr, rho, eps, n4);
-  int64_t tail = n - n4 * 4;
-  if (tail) k_adagrad_tail<<<1, 64, 0, s>>>(data, gsq, delta, inv_lr, rho, eps,
-                                            n4 * 4, n);
-}
-
-// sign = +1 for the default (add) updater, -1 for sgd.
-// Fat-block geometry (COPY_BLOCK x COPY_GRID): see the round-2 sweep
-// note at the COPY_BLOCK define.
-void mv_launch_sgd_copy(float* data, const float* delta, float* out,
-                        float sign, int64_t n, hipStream_t s) {
-  int64_t n4 = n / 4;
-  if (n4) k_sgd_copy_f4<<<grid_copy(n4), COPY_BLOCK, 0, s>>>(
-      (v4f*)data, (const v4f*)delta, (v4f*)out, sign, n4);
-  int64_t tail = n - n4 * 4;
-  if (tail) k_sgd_copy_tail<<<1, 64, 0, s>>>(data, delta, out, sign,
-                                             n4 * 4, n);
-}
-
-void mv_launch_momentum_copy(float* data, float* m, const float* delta,
-                             float* out, float mu, int64_t n, hipStream_t s) {
-  int64_t n4 = n / 4;
-  if (n4) k_momentum_copy_f4<<<grid_copy(n4), COPY_BLOCK, 0, s>>>(
-      (v4f*)data, (v4f*)m, (const v4f*)delta, (v4f*)out, mu, n4);
-  int64_t tail = n - n4 * 4;
-  if (tail) k_momentum_copy_tail<<<1, 64, 0, s>>>(data, m, delta, out, mu,
-                                                  n4 * 4, n);
-}
-
-void mv_launch_adagrad_copy(float* data, float* gsq, const float* delta,
-                            float* out, float lr, float rho, float eps,
-                            int64_t n, hipStream_t s) {
-  float inv_lr = 1.0f / lr;
-  int64_t n4 = n / 4;
-  if (n4) k_adagrad_copy_f4<<<grid_copy(n4), COPY_BLOCK, 0, s>>>(
-      (v4f*)data, (v4f*)gsq, (const v4f*)delta, (v4f*)out, inv_lr, rho, eps,
-      n4);
-  int64_t tail = n - n4 * 4;
-  if (tail) k_adagrad_copy_tail<<<1, 64, 0, s>>>(data, gsq, delta, out,
-                                                 inv_lr, rho, eps, n4 * 4, n);
-}
-
-void mv_launch_dcasgd_copy(float* data, float* bak, const float* delta,
-                           float* out, float lr, float lambda, int64_t n,
-                           hipStream_t s) {
-  int64_t n4 = n / 4;
-  if (n4) k_dcasgd_copy_f4<<<grid_copy(n4), COPY_BLOCK, 0, s>>>(
-      (v4f*)data, (v4f*)bak, (const v4f*)delta, (v4f*)out, lr, lambda, n4);
-  int64_t tail = n - n4 * 4;
-  if (tail) k_dcasgd_copy_tail<<<1, 64, 0, s>>>(data, bak, delta, out, lr,
-                                                lambda, n4 * 4, n);
-}
-
-void mv_launch_dcasgda_copy(float* data, float* bak, float* msq,
-                            const float* delta, float* out, float lr,
-                            float lambda, float rho, float eps, int64_t n,
-                            hipStream_t s) {
-  int64_t n4 = n / 4;
-  if (n4) k_dcasgda_copy_f4<<<grid_copy(n4), COPY_BLOCK, 0, s>>>(
-      (v4f*)data, (v4f*)bak, (v4f*)msq, (const v4f*)delta, (v4f*)out, lr,
-      lambda, rho, eps, n4);
-  int64_t tail = n - n4 * 4;
-  if (tail) k_dcasgda_copy_tail<<<1, 64, 0, s>>>(data, bak, msq, delta, out,
-                                                 lr, lambda, rho, eps,
-                                                 n4 * 4, n);
-}
-
-void mv_launch_dcasgd(float* data, float* bak, const float* delta,
-                      float lr, float lambda, int64_t n, hipStream_t s) {
-  int64_t n4 = n / 4;
-  if (n4) k_dcasgd_f4<<<grid_for_cap(n4, STATE_GRID), BLOCK, 0, s>>>(
-      (v4f*)data, (v4f*)bak, (const v4f*)delta, lr, lambda, n4);
-  int64_t tail = n - n4 * 4;
-  if (tail) k_dcasgd_tail<<<1, 64, 0, s>>>(data, bak, delta, lr, lambda,
-                                           n4 * 4, n);
-}
-
-void mv_launch_dcasgda(float* data, float* bak, float* msq, const float* delta,
-                       float lr, float lambda, float rho, float eps,
-                       int64_t n, hipStream_t s) {
-  int64_t n4 = n / 4;
-  if (n4) k_dcasgda_f4<<<grid_for_cap(n4, STATE_GRID), BLOCK, 0, s>>>(
-      (v4f*)data, (v4f*)bak, (v4f*)msq, (const v4f*)delta, lr, lambda, rho,
-      eps, n4);
-  int64_t tail = n - n4 * 4;
-  if (tail) k_dcasgda_tail<<<1, 64, 0, s>>>(data, bak, msq, delta, lr, lambda,
-                                            rho, eps, n4 * 4, n);
-}
 
 void mv_launch_row_gather(float* out, const float* shard, const int64_t* rows,
                           int64_t nrows, int64_t cols, hipStream_t s) {
   if (!nrows || !cols) return;
   int64_t total = nrows * cols;
   if (cols % 4 == 0 && total / 4 <= UINT32_MAX) {
-    k_row_gather_f4_u32<<<grid_for(total / 4), BLOCK, 0, s>>>(
+    k_row_gather<float4, uint32_t><<<grid_for(total / 4), BLOCK, 0, s>>>(
         (float4*)out, (const float4*)shard, rows, (uint32_t)(total / 4),
         (uint32_t)(cols / 4));
   } else if (cols % 4 == 0) {
-    int64_t cols4 = cols / 4;
-    k_row_gather_f4<<<grid_for(nrows * cols4), BLOCK, 0, s>>>(
-        (float4*)out, (const float4*)shard, rows, nrows, cols4);
+    k_row_gather<float4, int64_t><<<grid_for(total / 4), BLOCK, 0, s>>>(
+        (float4*)out, (const float4*)shard, rows, total / 4, cols / 4);
   } else if (cols % 2 == 0 && total / 2 <= UINT32_MAX) {
-    k_row_gather_f2_u32<<<grid_for(total / 2), BLOCK, 0, s>>>(
+    k_row_gather<float2, uint32_t><<<grid_for(total / 2), BLOCK, 0, s>>>(
         (float2*)out, (const float2*)shard, rows, (uint32_t)(total / 2),
         (uint32_t)(cols / 2));
   } else if (total <= UINT32_MAX) {
-    k_row_gather_u32<<<grid_for(total), BLOCK, 0, s>>>(
+    k_row_gather<float, uint32_t><<<grid_for(total), BLOCK, 0, s>>>(
         out, shard, rows, (uint32_t)total, (uint32_t)cols);
   } else {
-    k_row_gather<<<grid_for(total), BLOCK, 0, s>>>(
-        out, shard, rows, nrows, cols);
+    k_row_gather<float, int64_t><<<grid_for(total), BLOCK, 0, s>>>(
+        out, shard, rows, total, cols);
   }
 }
 
@@ -720,19 +440,46 @@ void mv_launch_row_scatter_add(float* shard, const float* vals,
                                int assume_unique, hipStream_t s) {
   if (!nrows || !cols) return;
   int64_t total = nrows * cols;
+  int grid = grid_for(total);
   if (total <= UINT32_MAX) {
+    uint32_t t = (uint32_t)total, c = (uint32_t)cols;
     if (assume_unique)
-      k_row_scatter_add_u_u32<<<grid_for(total), BLOCK, 0, s>>>(
-          shard, vals, rows, sign, (uint32_t)total, (uint32_t)cols);
+      k_row_scatter_add<uint32_t, false><<<grid, BLOCK, 0, s>>>(
+          shard, vals, rows, sign, t, c);
     else
-      k_row_scatter_add_u32<<<grid_for(total), BLOCK, 0, s>>>(
-          shard, vals, rows, sign, (uint32_t)total, (uint32_t)cols);
+      k_row_scatter_add<uint32_t, true><<<grid, BLOCK, 0, s>>>(
+          shard, vals, rows, sign, t, c);
   } else if (assume_unique) {
-    k_row_scatter_add_u<<<grid_for(total), BLOCK, 0, s>>>(
-        shard, vals, rows, sign, nrows, cols);
+    k_row_scatter_add<int64_t, false><<<grid, BLOCK, 0, s>>>(
+        shard, vals, rows, sign, total, cols);
   } else {
-    k_row_scatter_add<<<grid_for(total), BLOCK, 0, s>>>(
-        shard, vals, rows, sign, nrows, cols);
+    k_row_scatter_add<int64_t, true><<<grid, BLOCK, 0, s>>>(
+        shard, vals, rows, sign, total, cols);
+  }
+}
+
+void mv_launch_row_scatter_adagrad(
+    float* shard, float* gsq, const float* vals, const int64_t* rows,
+    float lr, float rho, float eps, int64_t nrows, int64_t cols,
+    int assume_unique, hipStream_t s) {
+  if (!nrows || !cols) return;
+  int64_t total = nrows * cols;
+  int grid = grid_for(total);
+  float inv_lr = 1.0f / lr;
+  if (total <= UINT32_MAX) {
+    uint32_t t = (uint32_t)total, c = (uint32_t)cols;
+    if (assume_unique)
+      k_row_scatter_adagrad<uint32_t, false><<<grid, BLOCK, 0, s>>>(
+          shard, gsq, vals, rows, inv_lr, rho, eps, t, c);
+    else
+      k_row_scatter_adagrad<uint32_t, true><<<grid, BLOCK, 0, s>>>(
+          shard, gsq, vals, rows, inv_lr, rho, eps, t, c);
+  } else if (assume_unique) {
+    k_row_scatter_adagrad<int64_t, false><<<grid, BLOCK, 0, s>>>(
+        shard, gsq, vals, rows, inv_lr, rho, eps, total, cols);
+  } else {
+    k_row_scatter_adagrad<int64_t, true><<<grid, BLOCK, 0, s>>>(
+        shard, gsq, vals, rows, inv_lr, rho, eps, total, cols);
   }
 }
 
@@ -759,6 +506,124 @@ void mv_launch_row_scatter_add(float* shard, const float* vals,
 // wordembedding.cpp:101-165 (G += g^2; w += g*lr0/rsqrt(G) when G>1e-10).
 // ---------------------------------------------------------------------------
 
+// Phase 1: h = mean of the group's input rows in_idx[ib..ie).
+template <int DPL>
+static __device__ __forceinline__ void w2v_hidden(
+    float (&h)[DPL], const float* __restrict__ in_emb,
+    const int64_t* __restrict__ in_idx, int ib, int ie, int dim, int lane) {
+  for (int i = ib; i < ie; ++i) {
+    const float* row = in_emb + in_idx[i] * dim;
+    // clamped UNCONDITIONAL loads: a divergent `if (c < dim)` around
+    // the load compiled to a branch + s_waitcnt vmcnt(0) PER DPL
+    // GROUP (full-latency serial, the round-2 ladder disease).
+    // min() keeps the read in-bounds; inactive lanes accumulate a
+    // duplicate element that nothing reads (wv[d]=0 gates every use).
+#pragma unroll
+    for (int d = 0; d < DPL; ++d) {
+      int c = lane + 64 * d;
+      h[d] += row[c < dim ? c : dim - 1];
+    }
+  }
+  if (ie - ib > 1) {
+    float inv = 1.f / (float)(ie - ib);
+#pragma unroll
+    for (int d = 0; d < DPL; ++d) h[d] *= inv;
+  }
+}
+
+// Phase 2: score output row `node` against h, step it towards `label`
+// (NS: 1 / 0; HS: the caller passes 1-code) and accumulate the hidden
+// error into err.
+template <int DPL, bool ADAGRAD, bool ATOMIC>
+static __device__ __forceinline__ void w2v_output(
+    const float (&h)[DPL], float (&err)[DPL], float* __restrict__ out_emb,
+    float* __restrict__ out_gsq, int64_t node, float label, float lr,
+    int dim, int lane) {
+  float* w = out_emb + node * dim;
+  float wv[DPL];
+  float f = 0.f;
+  // unconditional clamped load + select (see w2v_hidden): wv[d] MUST be
+  // 0 for inactive lanes (it feeds the wave-reduced dot), so the select
+  // stays — but on the value, not the load
+#pragma unroll
+  for (int d = 0; d < DPL; ++d) {
+    int c = lane + 64 * d;
+    float x = w[c < dim ? c : dim - 1];
+    wv[d] = (c < dim) ? x : 0.f;
+    f += h[d] * wv[d];
+  }
+#pragma unroll
+  for (int s = 32; s; s >>= 1) f += __shfl_xor(f, s, 64);
+  f = 1.f / (1.f + expf(-f));
+  float e = label - f;
+#pragma unroll
+  for (int d = 0; d < DPL; ++d) {
+    int c = lane + 64 * d;
+    if (c < dim) {
+      err[d] += e * wv[d];  // hidden_err uses the PRE-update classifier
+      if (ADAGRAD) {
+        float gg = e * h[d];
+        float* gq = out_gsq + node * dim + c;
+        float G2;
+        if (ATOMIC) G2 = atomicAdd(gq, gg * gg) + gg * gg;
+        else { G2 = *gq + gg * gg; *gq = G2; }
+        float dw = (G2 > 1e-10f) ? gg * lr * __frsqrt_rn(G2) : 0.f;
+        if (ATOMIC) atomicAdd(&w[c], dw);
+        else w[c] = wv[d] + dw;
+      } else {
+        if (ATOMIC) atomicAdd(&w[c], e * lr * h[d]);
+        else w[c] = wv[d] + e * lr * h[d];
+      }
+    }
+  }
+}
+
+// Phase 3: apply the accumulated hidden error to every input row.
+template <int DPL, bool ADAGRAD, bool ATOMIC>
+static __device__ __forceinline__ void w2v_writeback(
+    const float (&err)[DPL], float* __restrict__ in_emb,
+    float* __restrict__ in_gsq, const int64_t* __restrict__ in_idx,
+    int ib, int ie, float lr, int dim, int lane) {
+  for (int i = ib; i < ie; ++i) {
+    float* row = in_emb + in_idx[i] * dim;
+    if (!ADAGRAD && !ATOMIC) {
+      // hogwild-default path: branch-free rmw — unconditional clamped
+      // loads (issue back-to-back under one wait), guarded stores
+      float cur[DPL];
+#pragma unroll
+      for (int d = 0; d < DPL; ++d) {
+        int c = lane + 64 * d;
+        cur[d] = row[c < dim ? c : dim - 1];
+      }
+#pragma unroll
+      for (int d = 0; d < DPL; ++d) {
+        int c = lane + 64 * d;
+        if (c < dim) row[c] = cur[d] + lr * err[d];
+      }
+      continue;
+    }
+#pragma unroll
+    for (int d = 0; d < DPL; ++d) {
+      int c = lane + 64 * d;
+      if (c < dim) {
+        if (ADAGRAD) {
+          float* gq = in_gsq + in_idx[i] * dim + c;
+          float G2;
+          if (ATOMIC) G2 = atomicAdd(gq, err[d] * err[d]) + err[d] * err[d];
+          else { G2 = *gq + err[d] * err[d]; *gq = G2; }
+          float dw = (G2 > 1e-10f) ? err[d] * lr * __frsqrt_rn(G2) : 0.f;
+          if (ATOMIC) atomicAdd(&row[c], dw);
+          else row[c] += dw;
+        } else {
+          if (ATOMIC) atomicAdd(&row[c], lr * err[d]);
+          else row[c] += lr * err[d];
+        }
+      }
+    }
+  }
+}
+
+// General form: ragged out_idx/out_label lists per group.
 template <int DPL, bool ADAGRAD, bool ATOMIC>
 __global__ void k_w2v(float* __restrict__ in_emb, float* __restrict__ out_emb,
                       float* __restrict__ in_gsq, float* __restrict__ out_gsq,
@@ -776,101 +641,13 @@ __global__ void k_w2v(float* __restrict__ in_emb, float* __restrict__ out_emb,
 #pragma unroll
     for (int d = 0; d < DPL; ++d) { h[d] = 0.f; err[d] = 0.f; }
     int ib = in_off[g], ie = in_off[g + 1];
-    for (int i = ib; i < ie; ++i) {
-      const float* row = in_emb + in_idx[i] * dim;
-      // clamped UNCONDITIONAL loads: a divergent `if (c < dim)` around
-      // the load compiled to a branch + s_waitcnt vmcnt(0) PER DPL
-      // GROUP (full-latency serial, the round-2 ladder disease).
-      // min() keeps the read in-bounds; inactive lanes accumulate a
-      // duplicate element that nothing reads (wv[d]=0 gates every use).
-#pragma unroll
-      for (int d = 0; d < DPL; ++d) {
-        int c = lane + 64 * d;
-        h[d] += row[c < dim ? c : dim - 1];
-      }
-    }
-    if (ie - ib > 1) {
-      float inv = 1.f / (float)(ie - ib);
-#pragma unroll
-      for (int d = 0; d < DPL; ++d) h[d] *= inv;
-    }
+    w2v_hidden<DPL>(h, in_emb, in_idx, ib, ie, dim, lane);
     int ob = out_off[g], oe = out_off[g + 1];
-    for (int o = ob; o < oe; ++o) {
-      float* w = out_emb + out_idx[o] * dim;
-      float wv[DPL];
-      float f = 0.f;
-      // unconditional clamped load + select (see the h loop above):
-      // wv[d] MUST be 0 for inactive lanes (it feeds the wave-reduced
-      // dot), so the select stays — but on the value, not the load
-#pragma unroll
-      for (int d = 0; d < DPL; ++d) {
-        int c = lane + 64 * d;
-        float x = w[c < dim ? c : dim - 1];
-        wv[d] = (c < dim) ? x : 0.f;
-        f += h[d] * wv[d];
-      }
-#pragma unroll
-      for (int s = 32; s; s >>= 1) f += __shfl_xor(f, s, 64);
-      f = 1.f / (1.f + expf(-f));
-      float e = out_label[o] - f;  // NS: label-f; HS: caller passes 1-code
-#pragma unroll
-      for (int d = 0; d < DPL; ++d) {
-        int c = lane + 64 * d;
-        if (c < dim) {
-          err[d] += e * wv[d];  // hidden_err uses the PRE-update classifier
-          if (ADAGRAD) {
-            float gg = e * h[d];
-            float* gq = out_gsq + out_idx[o] * dim + c;
-            float G2;
-            if (ATOMIC) G2 = atomicAdd(gq, gg * gg) + gg * gg;
-            else { G2 = *gq + gg * gg; *gq = G2; }
-            float dw = (G2 > 1e-10f) ? gg * lr * __frsqrt_rn(G2) : 0.f;
-            if (ATOMIC) atomicAdd(&w[c], dw);
-            else w[c] = wv[d] + dw;
-          } else {
-            if (ATOMIC) atomicAdd(&w[c], e * lr * h[d]);
-            else w[c] = wv[d] + e * lr * h[d];
-          }
-        }
-      }
-    }
-    for (int i = ib; i < ie; ++i) {
-      float* row = in_emb + in_idx[i] * dim;
-      if (!ADAGRAD && !ATOMIC) {
-        // hogwild-default path: branch-free rmw — unconditional clamped
-        // loads (issue back-to-back under one wait), guarded stores
-        float cur[DPL];
-#pragma unroll
-        for (int d = 0; d < DPL; ++d) {
-          int c = lane + 64 * d;
-          cur[d] = row[c < dim ? c : dim - 1];
-        }
-#pragma unroll
-        for (int d = 0; d < DPL; ++d) {
-          int c = lane + 64 * d;
-          if (c < dim) row[c] = cur[d] + lr * err[d];
-        }
-        continue;
-      }
-#pragma unroll
-      for (int d = 0; d < DPL; ++d) {
-        int c = lane + 64 * d;
-        if (c < dim) {
-          if (ADAGRAD) {
-            float* gq = in_gsq + in_idx[i] * dim + c;
-            float G2;
-            if (ATOMIC) G2 = atomicAdd(gq, err[d] * err[d]) + err[d] * err[d];
-            else { G2 = *gq + err[d] * err[d]; *gq = G2; }
-            float dw = (G2 > 1e-10f) ? err[d] * lr * __frsqrt_rn(G2) : 0.f;
-            if (ATOMIC) atomicAdd(&row[c], dw);
-            else row[c] += dw;
-          } else {
-            if (ATOMIC) atomicAdd(&row[c], lr * err[d]);
-            else row[c] += lr * err[d];
-          }
-        }
-      }
-    }
+    for (int o = ob; o < oe; ++o)
+      w2v_output<DPL, ADAGRAD, ATOMIC>(h, err, out_emb, out_gsq, out_idx[o],
+                                       out_label[o], lr, dim, lane);
+    w2v_writeback<DPL, ADAGRAD, ATOMIC>(err, in_emb, in_gsq, in_idx, ib, ie,
+                                        lr, dim, lane);
   }
 }
 
@@ -901,24 +678,7 @@ __global__ void k_w2v_ns(float* __restrict__ in_emb, float* __restrict__ out_emb
     // in_off == nullptr: skip-gram (exactly one input per group) — the
     // offset loads vanish (probe V7: 5% over the ragged form)
     int ib = in_off ? in_off[g] : g, ie = in_off ? in_off[g + 1] : g + 1;
-    for (int i = ib; i < ie; ++i) {
-      const float* row = in_emb + in_idx[i] * dim;
-      // clamped UNCONDITIONAL loads: a divergent `if (c < dim)` around
-      // the load compiled to a branch + s_waitcnt vmcnt(0) PER DPL
-      // GROUP (full-latency serial, the round-2 ladder disease).
-      // min() keeps the read in-bounds; inactive lanes accumulate a
-      // duplicate element that nothing reads (wv[d]=0 gates every use).
-#pragma unroll
-      for (int d = 0; d < DPL; ++d) {
-        int c = lane + 64 * d;
-        h[d] += row[c < dim ? c : dim - 1];
-      }
-    }
-    if (ie - ib > 1) {
-      float inv = 1.f / (float)(ie - ib);
-#pragma unroll
-      for (int d = 0; d < DPL; ++d) h[d] *= inv;
-    }
+    w2v_hidden<DPL>(h, in_emb, in_idx, ib, ie, dim, lane);
     int64_t pos = centers[g];
     // per-group random stream (same recurrence as util.cpp:144)
     uint64_t next_random = seed + (uint64_t)g * 25214903917ull + 11ull;
@@ -933,83 +693,56 @@ __global__ void k_w2v_ns(float* __restrict__ in_emb, float* __restrict__ out_emb
         label = 0.f;
         if (node == pos) continue;  // wordembedding.cpp:279
       }
-      float* w = out_emb + node * dim;
-      float wv[DPL];
-      float f = 0.f;
-      // unconditional clamped load + select (see the h loop above):
-      // wv[d] MUST be 0 for inactive lanes (it feeds the wave-reduced
-      // dot), so the select stays — but on the value, not the load
-#pragma unroll
-      for (int d = 0; d < DPL; ++d) {
-        int c = lane + 64 * d;
-        float x = w[c < dim ? c : dim - 1];
-        wv[d] = (c < dim) ? x : 0.f;
-        f += h[d] * wv[d];
-      }
-#pragma unroll
-      for (int s = 32; s; s >>= 1) f += __shfl_xor(f, s, 64);
-      f = 1.f / (1.f + expf(-f));
-      float e = label - f;
-#pragma unroll
-      for (int d = 0; d < DPL; ++d) {
-        int c = lane + 64 * d;
-        if (c < dim) {
-          err[d] += e * wv[d];
-          if (ADAGRAD) {
-            float gg = e * h[d];
-            float* gq = out_gsq + node * dim + c;
-            float G2;
-            if (ATOMIC) G2 = atomicAdd(gq, gg * gg) + gg * gg;
-            else { G2 = *gq + gg * gg; *gq = G2; }
-            float dw = (G2 > 1e-10f) ? gg * lr * __frsqrt_rn(G2) : 0.f;
-            if (ATOMIC) atomicAdd(&w[c], dw);
-            else w[c] = wv[d] + dw;
-          } else {
-            if (ATOMIC) atomicAdd(&w[c], e * lr * h[d]);
-            else w[c] = wv[d] + e * lr * h[d];
-          }
-        }
-      }
+      w2v_output<DPL, ADAGRAD, ATOMIC>(h, err, out_emb, out_gsq, node, label,
+                                       lr, dim, lane);
     }
-    for (int i = ib; i < ie; ++i) {
-      float* row = in_emb + in_idx[i] * dim;
-      if (!ADAGRAD && !ATOMIC) {
-        // hogwild-default path: branch-free rmw — unconditional clamped
-        // loads (issue back-to-back under one wait), guarded stores
-        float cur[DPL];
-#pragma unroll
-        for (int d = 0; d < DPL; ++d) {
-          int c = lane + 64 * d;
-          cur[d] = row[c < dim ? c : dim - 1];
-        }
-#pragma unroll
-        for (int d = 0; d < DPL; ++d) {
-          int c = lane + 64 * d;
-          if (c < dim) row[c] = cur[d] + lr * err[d];
-        }
-        continue;
-      }
-#pragma unroll
-      for (int d = 0; d < DPL; ++d) {
-        int c = lane + 64 * d;
-        if (c < dim) {
-          if (ADAGRAD) {
-            float* gq = in_gsq + in_idx[i] * dim + c;
-            float G2;
-            if (ATOMIC) G2 = atomicAdd(gq, err[d] * err[d]) + err[d] * err[d];
-            else { G2 = *gq + err[d] * err[d]; *gq = G2; }
-            float dw = (G2 > 1e-10f) ? err[d] * lr * __frsqrt_rn(G2) : 0.f;
-            if (ATOMIC) atomicAdd(&row[c], dw);
-            else row[c] += dw;
-          } else {
-            if (ATOMIC) atomicAdd(&row[c], lr * err[d]);
-            else row[c] += lr * err[d];
-          }
-        }
-      }
-    }
+    w2v_writeback<DPL, ADAGRAD, ATOMIC>(err, in_emb, in_gsq, in_idx, ib, ie,
+                                        lr, dim, lane);
   }
 }
+
+// DPL register bucket for a row width: exact up to 8, then the next
+// instantiated bucket (the kernels guard c < dim, so oversize DPL only
+// costs idle iterations). Beyond 2048 columns the per-lane register
+// arrays (3*DPL VGPRs) would spill; that returns a DPL with no
+// instantiation, which the dispatch refuses LOUDLY instead of silently
+// doing nothing.
+static int w2v_dpl_bucket(int64_t dim) {
+  int dpl = (int)((dim + 63) / 64);
+  if (dpl > 8) dpl = (dpl <= 12) ? 12 : (dpl <= 16) ? 16
+                   : (dpl <= 24) ? 24 : (dpl <= 32) ? 32 : dpl;
+  return dpl;
+}
+
+// Launch KERNEL<DPL, ADAGRAD, ATOMIC> over G groups, one wave per group
+// (4 waves per 256-thread block).
+#define W2V_CASE(KERNEL, D, ...)                                             \
+  case D:                                                                    \
+    if (use_adagrad) {                                                       \
+      if (use_atomic) KERNEL<D, true, true><<<grid, BLOCK, 0, s>>>(__VA_ARGS__); \
+      else KERNEL<D, true, false><<<grid, BLOCK, 0, s>>>(__VA_ARGS__);       \
+    } else {                                                                 \
+      if (use_atomic) KERNEL<D, false, true><<<grid, BLOCK, 0, s>>>(__VA_ARGS__); \
+      else KERNEL<D, false, false><<<grid, BLOCK, 0, s>>>(__VA_ARGS__);      \
+    }                                                                        \
+    break;
+#define W2V_DISPATCH(KERNEL, ...)                                            \
+  do {                                                                       \
+    if (!G) return;                                                          \
+    int grid = grid_for(G * 64);                                             \
+    switch (w2v_dpl_bucket(dim)) {                                           \
+      W2V_CASE(KERNEL, 1, __VA_ARGS__) W2V_CASE(KERNEL, 2, __VA_ARGS__)      \
+      W2V_CASE(KERNEL, 3, __VA_ARGS__) W2V_CASE(KERNEL, 4, __VA_ARGS__)      \
+      W2V_CASE(KERNEL, 5, __VA_ARGS__) W2V_CASE(KERNEL, 6, __VA_ARGS__)      \
+      W2V_CASE(KERNEL, 7, __VA_ARGS__) W2V_CASE(KERNEL, 8, __VA_ARGS__)      \
+      W2V_CASE(KERNEL, 12, __VA_ARGS__) W2V_CASE(KERNEL, 16, __VA_ARGS__)    \
+      W2V_CASE(KERNEL, 24, __VA_ARGS__) W2V_CASE(KERNEL, 32, __VA_ARGS__)    \
+      default:                                                               \
+        fprintf(stderr, "%s: dim=%lld exceeds the 2048-column kernel "       \
+                "limit\n", __func__, (long long)dim);                        \
+        abort();                                                             \
+    }                                                                        \
+  } while (0)
 
 // Hogwild (plain-store) row updates by default — the reference's own
 // unsynchronized OpenMP trainers race identically (wordembedding.cpp
@@ -1024,41 +757,8 @@ extern "C" void mv_launch_w2v(float* in_emb, float* out_emb,
                               const int* out_off, float lr, int64_t G,
                               int64_t dim, int use_adagrad, int use_atomic,
                               hipStream_t s) {
-  if (!G) return;
-  int grid = grid_for(G * 64);  // 4 waves per 256-thread block
-  int dpl = (int)((dim + 63) / 64);
-#define W2V_LAUNCH(D, A, AT)                                                 \
-  k_w2v<D, A, AT><<<grid, BLOCK, 0, s>>>(in_emb, out_emb, in_gsq, out_gsq,   \
-      in_idx, in_off, out_idx, out_label, out_off, lr, (int)G, (int)dim)
-#define W2V_CASE(D)                                                          \
-  case D:                                                                    \
-    if (use_adagrad) {                                                       \
-      if (use_atomic) W2V_LAUNCH(D, true, true);                             \
-      else W2V_LAUNCH(D, true, false);                                       \
-    } else {                                                                 \
-      if (use_atomic) W2V_LAUNCH(D, false, true);                            \
-      else W2V_LAUNCH(D, false, false);                                      \
-    }                                                                        \
-    break;
-  // dpl > 8 rounds up to the next instantiated register bucket (the
-  // kernel guards c < dim, so oversize DPL only costs idle iterations);
-  // beyond 2048 columns the per-lane register arrays (3*DPL VGPRs)
-  // would spill — refuse LOUDLY instead of silently doing nothing
-  // (VERDICT r1 weak #6).
-  if (dpl > 8) dpl = (dpl <= 12) ? 12 : (dpl <= 16) ? 16
-                   : (dpl <= 24) ? 24 : (dpl <= 32) ? 32 : dpl;
-  switch (dpl) {
-    W2V_CASE(1) W2V_CASE(2) W2V_CASE(3) W2V_CASE(4)
-    W2V_CASE(5) W2V_CASE(6) W2V_CASE(7) W2V_CASE(8)
-    W2V_CASE(12) W2V_CASE(16) W2V_CASE(24) W2V_CASE(32)
-    default:
-      fprintf(stderr,
-              "mv_launch_w2v: dim=%lld exceeds the 2048-column kernel "
-              "limit\n", (long long)dim);
-      abort();
-  }
-#undef W2V_CASE
-#undef W2V_LAUNCH
+  W2V_DISPATCH(k_w2v, in_emb, out_emb, in_gsq, out_gsq, in_idx, in_off,
+               out_idx, out_label, out_off, lr, (int)G, (int)dim);
 }
 
 extern "C" void mv_launch_w2v_ns(float* in_emb, float* out_emb,
@@ -1069,38 +769,11 @@ extern "C" void mv_launch_w2v_ns(float* in_emb, float* out_emb,
                                  int neg, uint64_t seed, float lr, int64_t G,
                                  int64_t dim, int use_adagrad, int use_atomic,
                                  hipStream_t s) {
-  if (!G) return;
-  int grid = grid_for(G * 64);
-  int dpl = (int)((dim + 63) / 64);
-#define W2VNS_LAUNCH(D, A, AT)                                               \
-  k_w2v_ns<D, A, AT><<<grid, BLOCK, 0, s>>>(in_emb, out_emb, in_gsq,         \
-      out_gsq, in_idx, in_off, centers, pool, pool_n, neg, seed, lr,         \
-      (int)G, (int)dim)
-#define W2VNS_CASE(D)                                                        \
-  case D:                                                                    \
-    if (use_adagrad) {                                                       \
-      if (use_atomic) W2VNS_LAUNCH(D, true, true);                           \
-      else W2VNS_LAUNCH(D, true, false);                                     \
-    } else {                                                                 \
-      if (use_atomic) W2VNS_LAUNCH(D, false, true);                          \
-      else W2VNS_LAUNCH(D, false, false);                                    \
-    }                                                                        \
-    break;
-  if (dpl > 8) dpl = (dpl <= 12) ? 12 : (dpl <= 16) ? 16
-                   : (dpl <= 24) ? 24 : (dpl <= 32) ? 32 : dpl;
-  switch (dpl) {
-    W2VNS_CASE(1) W2VNS_CASE(2) W2VNS_CASE(3) W2VNS_CASE(4)
-    W2VNS_CASE(5) W2VNS_CASE(6) W2VNS_CASE(7) W2VNS_CASE(8)
-    W2VNS_CASE(12) W2VNS_CASE(16) W2VNS_CASE(24) W2VNS_CASE(32)
-    default:
-      fprintf(stderr,
-              "mv_launch_w2v_ns: dim=%lld exceeds the 2048-column kernel "
-              "limit\n", (long long)dim);
-      abort();
-  }
-#undef W2VNS_CASE
-#undef W2VNS_LAUNCH
+  W2V_DISPATCH(k_w2v_ns, in_emb, out_emb, in_gsq, out_gsq, in_idx, in_off,
+               centers, pool, pool_n, neg, seed, lr, (int)G, (int)dim);
 }
+#undef W2V_DISPATCH
+#undef W2V_CASE
 
 // ---------------------------------------------------------------------------
 // Fused sparse logistic regression minibatch (K13/K14 fused): the
@@ -1189,119 +862,6 @@ extern "C" void mv_launch_lr_sigmoid_scatter(
   if (!B) return;
   k_lr_sigmoid_scatter<<<grid_for(B * 64), BLOCK, 0, s>>>(
       w, keys, vals, ptr, err, lr, reg_type, reg_coef, (int)B);
-}
-
-// ---------------------------------------------------------------------------
-// Keyed AdaGrad scatter-update (K15 + K4 keyed form): for each incoming
-// (row, value) pair apply the adagrad step to the owned shard row. Used by
-// the LogisticRegression sparse path (BASELINE config: 1e9 sparse
-// features, AdaGrad updater). Duplicate rows race benignly (hogwild):
-// G accumulates via atomicAdd; the weight step uses the post-add G.
-// ---------------------------------------------------------------------------
-
-__global__ void k_row_scatter_adagrad(float* __restrict__ shard,
-                                      float* __restrict__ gsq,
-                                      const float* __restrict__ vals,
-                                      const int64_t* __restrict__ rows,
-                                      float inv_lr, float rho, float eps,
-                                      int64_t nrows, int64_t cols) {
-  int64_t total = nrows * cols;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    int64_t r = i / cols, c = i % cols;
-    int64_t k = rows[r] * cols + c;
-    float g = vals[i] * inv_lr;
-    if (g != 0.0f) {
-      float G = atomicAdd(&gsq[k], g * g) + g * g;
-      atomicAdd(&shard[k], -rho * g * __frsqrt_rn(G + eps));
-    }
-  }
-}
-
-__global__ void k_row_scatter_adagrad_u(float* __restrict__ shard,
-                                        float* __restrict__ gsq,
-                                        const float* __restrict__ vals,
-                                        const int64_t* __restrict__ rows,
-                                        float inv_lr, float rho, float eps,
-                                        int64_t nrows, int64_t cols) {
-  int64_t total = nrows * cols;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    int64_t r = i / cols, c = i % cols;
-    int64_t k = rows[r] * cols + c;
-    float g = vals[i] * inv_lr;
-    if (g != 0.0f) {
-      float G = gsq[k] + g * g;
-      gsq[k] = G;
-      shard[k] -= rho * g * __frsqrt_rn(G + eps);
-    }
-  }
-}
-
-// u32 loop-index forms (one 64-bit divide per element is real VALU
-// time; shard/gsq offsets stay 64-bit for 1e9-row tables)
-__global__ void k_row_scatter_adagrad_u32(float* __restrict__ shard,
-                                          float* __restrict__ gsq,
-                                          const float* __restrict__ vals,
-                                          const int64_t* __restrict__ rows,
-                                          float inv_lr, float rho, float eps,
-                                          uint32_t total, uint32_t cols) {
-  uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += stride) {
-    uint32_t r = i / cols, c = i - r * cols;
-    int64_t k = rows[r] * (int64_t)cols + c;
-    float g = vals[i] * inv_lr;
-    if (g != 0.0f) {
-      float G = atomicAdd(&gsq[k], g * g) + g * g;
-      atomicAdd(&shard[k], -rho * g * __frsqrt_rn(G + eps));
-    }
-  }
-}
-
-__global__ void k_row_scatter_adagrad_u_u32(float* __restrict__ shard,
-                                            float* __restrict__ gsq,
-                                            const float* __restrict__ vals,
-                                            const int64_t* __restrict__ rows,
-                                            float inv_lr, float rho,
-                                            float eps, uint32_t total,
-                                            uint32_t cols) {
-  uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += stride) {
-    uint32_t r = i / cols, c = i - r * cols;
-    int64_t k = rows[r] * (int64_t)cols + c;
-    float g = vals[i] * inv_lr;
-    if (g != 0.0f) {
-      float G = gsq[k] + g * g;
-      gsq[k] = G;
-      shard[k] -= rho * g * __frsqrt_rn(G + eps);
-    }
-  }
-}
-
-extern "C" void mv_launch_row_scatter_adagrad(
-    float* shard, float* gsq, const float* vals, const int64_t* rows,
-    float lr, float rho, float eps, int64_t nrows, int64_t cols,
-    int assume_unique, hipStream_t s) {
-  if (!nrows || !cols) return;
-  int64_t total = nrows * cols;
-  if (total <= UINT32_MAX) {
-    if (assume_unique)
-      k_row_scatter_adagrad_u_u32<<<grid_for(total), BLOCK, 0, s>>>(
-          shard, gsq, vals, rows, 1.0f / lr, rho, eps, (uint32_t)total,
-          (uint32_t)cols);
-    else
-      k_row_scatter_adagrad_u32<<<grid_for(total), BLOCK, 0, s>>>(
-          shard, gsq, vals, rows, 1.0f / lr, rho, eps, (uint32_t)total,
-          (uint32_t)cols);
-  } else if (assume_unique) {
-    k_row_scatter_adagrad_u<<<grid_for(total), BLOCK, 0, s>>>(
-        shard, gsq, vals, rows, 1.0f / lr, rho, eps, nrows, cols);
-  } else {
-    k_row_scatter_adagrad<<<grid_for(total), BLOCK, 0, s>>>(
-        shard, gsq, vals, rows, 1.0f / lr, rho, eps, nrows, cols);
-  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1594,103 +1154,6 @@ extern "C" void mv_launch_lr_ftrl_scatter(
   k_lr_ftrl_scatter<<<grid_for(B * 64), BLOCK, 0, s>>>(
       zn, keys, vals, ptr, err, alpha_inv, beta, l1, l2, (int)B, (int)K);
 }
-
-// ---------------------------------------------------------------------------
-// dtype-generic elementwise updaters. The reference instantiates its
-// tables for int/float/double (array_table.cpp:153-154); fp32 keeps the
-// tuned float4/nontemporal path above, and these scalar grid-stride
-// forms carry double (all updaters) and int32/int64 (plain add — the
-// reference's int specialization is add-only, updater.cpp:40-43).
-// Still memory-bound: 8B scalar accesses per lane stream HBM fine for
-// these parity paths.
-// ---------------------------------------------------------------------------
-
-template <typename T>
-__global__ void k_add_g(T* __restrict__ data, const T* __restrict__ delta,
-                        int64_t n) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride)
-    data[i] += delta[i];
-}
-
-template <typename T>
-__global__ void k_sgd_g(T* __restrict__ data, const T* __restrict__ delta,
-                        int64_t n) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride)
-    data[i] -= delta[i];
-}
-
-template <typename T>
-__global__ void k_momentum_g(T* __restrict__ data, T* __restrict__ m,
-                             const T* __restrict__ delta, T mu, int64_t n) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride) {
-    T mm = mu * m[i] + ((T)1 - mu) * delta[i];
-    m[i] = mm;
-    data[i] -= mm;
-  }
-}
-
-template <typename T>
-__global__ void k_adagrad_g(T* __restrict__ data, T* __restrict__ gsq,
-                            const T* __restrict__ delta, T inv_lr, T rho,
-                            T eps, int64_t n) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride) {
-    T g = delta[i] * inv_lr;
-    T G = gsq[i] + g * g;
-    gsq[i] = G;
-    data[i] -= rho * g / sqrt(G + eps);
-  }
-}
-
-template <typename T>
-__global__ void k_sgd_copy_g(T* __restrict__ data,
-                             const T* __restrict__ delta,
-                             T* __restrict__ out, T sign, int64_t n) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride) {
-    T v = data[i] + sign * delta[i];
-    data[i] = v;
-    out[i] = v;
-  }
-}
-
-extern "C" {
-void mv_launch_add_f64(double* d, const double* x, int64_t n, hipStream_t s) {
-  if (n > 0) k_add_g<double><<<grid_for_cap(n, ELEM_GRID), BLOCK, 0, s>>>(d, x, n);
-}
-void mv_launch_sgd_f64(double* d, const double* x, int64_t n, hipStream_t s) {
-  if (n > 0) k_sgd_g<double><<<grid_for_cap(n, ELEM_GRID), BLOCK, 0, s>>>(d, x, n);
-}
-void mv_launch_momentum_f64(double* d, double* m, const double* x, double mu,
-                            int64_t n, hipStream_t s) {
-  if (n > 0) k_momentum_g<double><<<grid_for_cap(n, STATE_GRID), BLOCK, 0, s>>>(
-      d, m, x, mu, n);
-}
-void mv_launch_adagrad_f64(double* d, double* g, const double* x, double lr,
-                           double rho, double eps, int64_t n, hipStream_t s) {
-  if (n > 0) k_adagrad_g<double><<<grid_for_cap(n, STATE_GRID), BLOCK, 0, s>>>(
-      d, g, x, 1.0 / lr, rho, eps, n);
-}
-void mv_launch_sgd_copy_f64(double* d, const double* x, double* out,
-                            double sign, int64_t n, hipStream_t s) {
-  if (n > 0) k_sgd_copy_g<double><<<grid_for_cap(n, STATE_GRID), BLOCK, 0, s>>>(
-      d, x, out, sign, n);
-}
-void mv_launch_add_i32(int32_t* d, const int32_t* x, int64_t n, hipStream_t s) {
-  if (n > 0) k_add_g<int32_t><<<grid_for_cap(n, ELEM_GRID), BLOCK, 0, s>>>(d, x, n);
-}
-void mv_launch_add_i64(int64_t* d, const int64_t* x, int64_t n, hipStream_t s) {
-  if (n > 0) k_add_g<int64_t><<<grid_for_cap(n, ELEM_GRID), BLOCK, 0, s>>>(d, x, n);
-}
-}  // extern "C"
 
 // ---------------------------------------------------------------------------
 // Dense-mode minibatch post-GEMM fusion (reference sparse=false — its

@@ -36,7 +36,7 @@ def test_sgd(hip, n):
     assert torch.equal(data, ref)
 
 
-@pytest.mark.parametrize("n", [64, 999, 1 << 18])
+@pytest.mark.parametrize("n", [1, 3, 5, 64, 999, 1 << 18])
 def test_momentum(hip, n):
     data, m, delta = rand(n, 5), rand(n, 6).abs(), rand(n, 7)
     mu = 0.9
@@ -50,7 +50,7 @@ def test_momentum(hip, n):
     assert torch.allclose(data, ref_d, rtol=1e-6, atol=1e-5)
 
 
-@pytest.mark.parametrize("n", [64, 999, 1 << 18])
+@pytest.mark.parametrize("n", [1, 3, 5, 64, 999, 1 << 18])
 def test_adagrad(hip, n):
     data, gsq, delta = rand(n, 8), rand(n, 9).abs(), rand(n, 10)
     lr, rho, eps = 0.1, 0.05, 1e-6
@@ -63,7 +63,7 @@ def test_adagrad(hip, n):
     assert torch.allclose(data, ref_d, rtol=1e-4, atol=1e-5)
 
 
-@pytest.mark.parametrize("n", [64, 999, 1 << 18])
+@pytest.mark.parametrize("n", [1, 3, 5, 64, 999, 1 << 18])
 def test_dcasgd(hip, n):
     data, bak, delta = rand(n, 20), rand(n, 21), rand(n, 22)
     lr, lam = 0.1, 0.04
@@ -74,7 +74,7 @@ def test_dcasgd(hip, n):
     assert torch.equal(bak, data)
 
 
-@pytest.mark.parametrize("n", [64, 999, 1 << 18])
+@pytest.mark.parametrize("n", [1, 3, 5, 64, 999, 1 << 18])
 def test_dcasgda(hip, n):
     data, bak, msq, delta = rand(n, 23), rand(n, 24), rand(n, 25).abs(), \
         rand(n, 26)
@@ -87,6 +87,104 @@ def test_dcasgda(hip, n):
     assert torch.allclose(msq, ref_m, rtol=1e-5, atol=1e-7)
     assert torch.allclose(data, ref, rtol=1e-4, atol=1e-5)
     assert torch.equal(bak, data)
+
+
+# Sizes at which the float4-body / scalar-tail split can go wrong:
+# tail only (1, 3), body only (4), both (5, 1027).
+SPLIT_SIZES = [1, 3, 4, 5, 1027]
+
+# Stateful updaters: state tensors (after data) and scalar arguments, the
+# values test_momentum / test_adagrad / test_dcasgd / test_dcasgda use.
+FUSED_STATE = {"momentum": ("m",), "adagrad": ("gsq",), "dcasgd": ("bak",),
+               "dcasgda": ("bak", "msq")}
+FUSED_ARGS = {"momentum": (0.9,), "adagrad": (0.1, 0.05, 1e-6),
+              "dcasgd": (0.1, 0.04), "dcasgda": (0.1, 0.04, 0.95, 1e-7)}
+
+
+def fused_reference(name, data, state, delta):
+    """[(reference, rtol, atol)] for data and then each state tensor: the
+    torch formulas and tolerances of test_momentum ... test_dcasgda."""
+    if name == "momentum":
+        mu, = FUSED_ARGS[name]
+        m = mu * state[0] + (1 - mu) * delta
+        return [(data - m, 1e-6, 1e-5), (m, 1e-6, 1e-6)]
+    if name == "adagrad":
+        lr, rho, eps = FUSED_ARGS[name]
+        g = delta / lr
+        G = state[0] + g * g
+        return [(data - rho * g / torch.sqrt(G + eps), 1e-4, 1e-5),
+                (G, 1e-5, 1e-6)]
+    if name == "dcasgd":
+        lr, lam = FUSED_ARGS[name]
+        w = data - lr * (delta + lam * delta * delta * (data - state[0]))
+        return [(w, 1e-5, 1e-6), (w, 1e-5, 1e-6)]
+    lr, lam, rho, eps = FUSED_ARGS[name]
+    bak, msq = state
+    m = rho * msq + (1 - rho) * delta * delta
+    w = data - lr * (delta + lam / torch.sqrt(m + eps) * delta * delta
+                     * (data - bak))
+    return [(w, 1e-4, 1e-5), (w, 1e-4, 1e-5), (m, 1e-5, 1e-7)]
+
+
+@pytest.mark.parametrize("n", SPLIT_SIZES)
+@pytest.mark.parametrize("name", list(FUSED_STATE))
+def test_fused_copy_entry_points(hip, name, n):
+    """The fused Add+Get entry points called directly: torch formula,
+    out == data, and bit-identical to the non-copy entry point."""
+    data, delta = rand(n, 30), rand(n, 31)
+    state = [rand(n, 32 + k) if s == "bak" else rand(n, 32 + k).abs()
+             for k, s in enumerate(FUSED_STATE[name])]
+    want = fused_reference(name, data, state, delta)
+    plain = [t.clone() for t in [data] + state]
+    out = torch.full_like(data, float("nan"))
+    getattr(hip, name + "_copy_update")(data, *state, delta, out,
+                                        *FUSED_ARGS[name])
+    getattr(hip, name + "_update")(*plain, delta, *FUSED_ARGS[name])
+    torch.cuda.synchronize()
+    for got, (ref, rtol, atol) in zip([data] + state, want):
+        assert torch.allclose(got, ref, rtol=rtol, atol=atol), \
+            (got - ref).abs().max()
+    if FUSED_STATE[name][0] == "bak":
+        assert torch.equal(state[0], data)
+    assert torch.equal(out, data)
+    for got, same in zip([data] + state, plain):
+        assert torch.equal(got, same)
+
+
+@pytest.mark.parametrize("n", SPLIT_SIZES)
+@pytest.mark.parametrize("sign", [1.0, -1.0])
+def test_sgd_copy_entry_point(hip, sign, n):
+    """sgd_copy_update called directly. sign * delta is exact for +-1, so
+    the result is the single rounding of test_add / test_sgd: exact."""
+    data, delta = rand(n, 40), rand(n, 41)
+    ref = data + sign * delta
+    plain = data.clone()
+    out = torch.full_like(data, float("nan"))
+    hip.sgd_copy_update(data, delta, out, sign)
+    (hip.add_inplace if sign > 0 else hip.sgd_update)(plain, delta)
+    torch.cuda.synchronize()
+    assert torch.equal(data, ref)
+    assert torch.equal(out, data)
+    assert torch.equal(plain, data)
+
+
+def test_small_f64_and_int_updaters(hip):
+    """n = 5 through the double and integer instantiations: exact."""
+    g = torch.Generator(device="cpu").manual_seed(42)
+    d = torch.randn(5, generator=g, dtype=torch.float64).cuda()
+    x = torch.randn(5, generator=g, dtype=torch.float64).cuda()
+    out = torch.full_like(d, float("nan"))
+    ref = d - x
+    hip.sgd_copy_update(d, x, out, -1.0)
+    torch.cuda.synchronize()
+    assert torch.equal(d, ref) and torch.equal(out, ref)
+    for dt in (torch.int32, torch.int64):
+        d = torch.randint(-100, 100, (5,), generator=g, dtype=dt).cuda()
+        x = torch.randint(-100, 100, (5,), generator=g, dtype=dt).cuda()
+        ref = d + x
+        hip.add_inplace(d, x)
+        torch.cuda.synchronize()
+        assert torch.equal(d, ref)
 
 
 @pytest.mark.parametrize("cols", [128, 200, 10, 2, 7])
@@ -109,6 +207,22 @@ def test_row_scatter_add(hip, cols):
     hip.row_scatter_add(shard, rows, vals, -1.0)
     torch.cuda.synchronize()
     assert torch.allclose(shard, ref, rtol=1e-5, atol=1e-5)
+
+
+@pytest.mark.parametrize("cols", [7, 128])
+def test_row_scatter_add_unique(hip, cols):
+    """assume_unique=True (plain read-modify-write, no atomics) on unique
+    rows. Each element takes one add of -vals on either side (sign = -1
+    is exact), so the result equals index_add_ exactly."""
+    shard = rand(300 * cols, 14).view(300, cols)
+    ref = shard.clone()
+    g = torch.Generator(device="cpu").manual_seed(16)
+    rows = torch.randperm(300, generator=g)[:128].cuda()
+    vals = rand(128 * cols, 15).view(128, cols)
+    ref.index_add_(0, rows, -vals)
+    hip.row_scatter_add(shard, rows, vals, -1.0, True)
+    torch.cuda.synchronize()
+    assert torch.equal(shard, ref)
 
 
 def test_table_ops_gpu():

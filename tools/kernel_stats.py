@@ -27,7 +27,11 @@ def summarize(path: str) -> str:
     out = ["| kernel | calls | total ms | avg us | % |",
            "|---|---|---|---|---|"]
     for name, calls, tot, avg in rows:
-        short = name.split("(")[0][:70]
+        # drop the parameter list; "float __vector(4)" inside template
+        # arguments (k_elem<SgdOp<float>, float __vector(4), true>) stays
+        short = name.split(">(")[0] + ">" if ">(" in name else \
+            name.split("(")[0]
+        short = short[:70]
         out.append(f"| {short} | {calls} | {tot/1e6:.3f} | "
                    f"{avg/1e3:.2f} | {100*tot/total:.1f} |")
     return "\n".join(out)
