@@ -52,6 +52,17 @@ void mv_launch_lr_sigmoid_scatter(float*, const int64_t*, const float*,
 void mv_launch_row_scatter_adagrad(float*, float*, const float*,
                                    const int64_t*, float, float, float,
                                    int64_t, int64_t, int, hipStream_t);
+// keyed stateful updaters: (shard, state..., vals, rows, perm-or-null,
+// scalars..., nrows, cols)
+void mv_launch_row_momentum(float*, float*, const float*, const int64_t*,
+                            const int64_t*, float, int64_t, int64_t,
+                            hipStream_t);
+void mv_launch_row_dcasgd(float*, float*, const float*, const int64_t*,
+                          const int64_t*, float, float, int64_t, int64_t,
+                          hipStream_t);
+void mv_launch_row_dcasgda(float*, float*, float*, const float*,
+                           const int64_t*, const int64_t*, float, float,
+                           float, float, int64_t, int64_t, hipStream_t);
 void mv_launch_lr_softmax_fwd(const float*, const int64_t*, const float*,
                               const int*, const float*, const float*,
                               float*, float*, int64_t, int64_t, hipStream_t);
@@ -295,6 +306,63 @@ void row_scatter_adagrad(torch::Tensor shard, torch::Tensor gsq,
       shard.data_ptr<float>(), gsq.data_ptr<float>(), vals.data_ptr<float>(),
       rows.data_ptr<int64_t>(), (float)lr, (float)rho, (float)eps,
       rows.numel(), shard.size(1), assume_unique ? 1 : 0, cur_stream());
+}
+
+// Validation shared by the keyed stateful updaters; returns perm's data
+// pointer, or null for the identity.
+const int64_t* check_row_update(const torch::Tensor& shard,
+                                std::initializer_list<Named> state,
+                                const torch::Tensor& rows,
+                                const torch::Tensor& vals,
+                                const c10::optional<torch::Tensor>& perm) {
+  check_f32(shard, "shard"); check_f32(vals, "vals");
+  TORCH_CHECK(shard.dim() == 2, "shard must be 2-D");
+  for (const auto& t : state) {
+    check_f32(t.second, t.first);
+    TORCH_CHECK(t.second.sizes() == shard.sizes(), t.first,
+                " shape mismatch");
+  }
+  TORCH_CHECK(rows.scalar_type() == torch::kInt64 && rows.is_cuda() &&
+              rows.is_contiguous(), "rows must be contiguous int64 on GPU");
+  TORCH_CHECK(vals.numel() == rows.numel() * shard.size(1), "vals mismatch");
+  if (!perm.has_value()) return nullptr;
+  TORCH_CHECK(perm->scalar_type() == torch::kInt64 && perm->is_cuda() &&
+              perm->is_contiguous(), "perm must be contiguous int64 on GPU");
+  TORCH_CHECK(perm->numel() == rows.numel(), "perm size mismatch");
+  return perm->data_ptr<int64_t>();
+}
+
+void row_momentum_update(torch::Tensor shard, torch::Tensor m,
+                         torch::Tensor rows, torch::Tensor vals, double mu,
+                         c10::optional<torch::Tensor> perm) {
+  const int64_t* pp = check_row_update(shard, {{"m", m}}, rows, vals, perm);
+  mv_launch_row_momentum(f32(shard), f32(m), f32(vals),
+                         rows.data_ptr<int64_t>(), pp, (float)mu,
+                         rows.numel(), shard.size(1), cur_stream());
+}
+
+void row_dcasgd_update(torch::Tensor shard, torch::Tensor bak,
+                       torch::Tensor rows, torch::Tensor vals, double lr,
+                       double lambda, c10::optional<torch::Tensor> perm) {
+  const int64_t* pp = check_row_update(shard, {{"bak", bak}}, rows, vals,
+                                       perm);
+  mv_launch_row_dcasgd(f32(shard), f32(bak), f32(vals),
+                       rows.data_ptr<int64_t>(), pp, (float)lr,
+                       (float)lambda, rows.numel(), shard.size(1),
+                       cur_stream());
+}
+
+void row_dcasgda_update(torch::Tensor shard, torch::Tensor bak,
+                        torch::Tensor msq, torch::Tensor rows,
+                        torch::Tensor vals, double lr, double lambda,
+                        double rho, double eps,
+                        c10::optional<torch::Tensor> perm) {
+  const int64_t* pp = check_row_update(shard, {{"bak", bak}, {"msq", msq}},
+                                       rows, vals, perm);
+  mv_launch_row_dcasgda(f32(shard), f32(bak), f32(msq), f32(vals),
+                        rows.data_ptr<int64_t>(), pp, (float)lr,
+                        (float)lambda, (float)rho, (float)eps, rows.numel(),
+                        shard.size(1), cur_stream());
 }
 
 void w2v_train(torch::Tensor in_emb, torch::Tensor out_emb,
@@ -614,6 +682,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("shard"), py::arg("gsq"), py::arg("rows"), py::arg("vals"),
         py::arg("lr"), py::arg("rho"), py::arg("eps"),
         py::arg("assume_unique") = false);
+  m.def("row_momentum_update", &row_momentum_update,
+        "keyed momentum: sum value rows per row id (equal ids adjacent in "
+        "rows; perm maps list position to vals row), one step per row",
+        py::arg("shard"), py::arg("m"), py::arg("rows"), py::arg("vals"),
+        py::arg("mu"), py::arg("perm") = py::none());
+  m.def("row_dcasgd_update", &row_dcasgd_update,
+        "keyed DC-ASGD, same row/perm contract as row_momentum_update",
+        py::arg("shard"), py::arg("bak"), py::arg("rows"), py::arg("vals"),
+        py::arg("lr"), py::arg("lam"), py::arg("perm") = py::none());
+  m.def("row_dcasgda_update", &row_dcasgda_update,
+        "keyed DC-ASGD-a, same row/perm contract as row_momentum_update",
+        py::arg("shard"), py::arg("bak"), py::arg("msq"), py::arg("rows"),
+        py::arg("vals"), py::arg("lr"), py::arg("lam"), py::arg("rho"),
+        py::arg("eps"), py::arg("perm") = py::none());
   m.def("w2v_train", &w2v_train,
         "K9-K11: fused word2vec block training (skip-gram/CBOW, NS/HS, "
         "optional adagrad)");

@@ -107,6 +107,9 @@ static inline int grid_for(int64_t work_items) {
 // updater.cpp:40-43) run the same ops with V = T, plain scalar access.
 // Every step issues all its loads before its first store: struct members
 // carry no __restrict__, so a load written after a store would wait for it.
+// The momentum and DC-ASGD ops keep their formula in step_at<V>(i, g), which
+// takes the gradient as a value (step loads it from delta first): the
+// row-keyed k_row_update below hands it a per-row sum instead.
 // ---------------------------------------------------------------------------
 
 template <class T>
@@ -137,17 +140,20 @@ template <class T>
 struct MomentumOp {
   using elem = T;
   T* data; T* m; const T* delta; T mu;
-  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+  template <class V> __device__ __forceinline__ V step_at(int64_t i,
+                                                          V g) const {
     V d = ld<V>(data, i);
     // explicit fma, so that every instantiation rounds alike: left to
     // contract on its own, the compiler fused mu*m + (1-mu)*delta in the
     // float4 bodies and the fused tail but not in the plain scalar tail
-    V mm = __builtin_elementwise_fma((V)mu, ld<V>(m, i),
-                                     ((T)1 - mu) * ld<V>(delta, i));
+    V mm = __builtin_elementwise_fma((V)mu, ld<V>(m, i), ((T)1 - mu) * g);
     st(m, i, mm);
     d -= mm;
     st(data, i, d);
     return d;
+  }
+  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+    return step_at<V>(i, ld<V>(delta, i));
   }
 };
 
@@ -182,13 +188,16 @@ struct AdagradOp {
 struct DcasgdOp {
   using elem = float;
   float* data; float* bak; const float* delta; float lr, lambda;
-  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+  template <class V> __device__ __forceinline__ V step_at(int64_t i,
+                                                          V g) const {
     V w = ld<V>(data, i), b = ld<V>(bak, i);
-    V g = ld<V>(delta, i);
     w -= lr * (g + lambda * g * g * (w - b));
     st(data, i, w);
     st(bak, i, w);
     return w;
+  }
+  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+    return step_at<V>(i, ld<V>(delta, i));
   }
 };
 
@@ -196,9 +205,9 @@ struct DcasgdaOp {
   using elem = float;
   float* data; float* bak; float* msq; const float* delta;
   float lr, lambda, rho, eps;
-  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+  template <class V> __device__ __forceinline__ V step_at(int64_t i,
+                                                          V g) const {
     V w = ld<V>(data, i), b = ld<V>(bak, i);
-    V g = ld<V>(delta, i);
     V m = rho * ld<V>(msq, i) + (1.0f - rho) * g * g;
     st(msq, i, m);
     V lam = lambda * rsq(m + eps);
@@ -206,6 +215,9 @@ struct DcasgdaOp {
     st(data, i, w);
     st(bak, i, w);
     return w;
+  }
+  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+    return step_at<V>(i, ld<V>(delta, i));
   }
 };
 
@@ -408,7 +420,108 @@ __global__ void k_row_scatter_adagrad(float* __restrict__ shard,
   }
 }
 
+// Keyed stateful update (momentum, dcasgd, dcasgda; the per-row
+// updater_->Update(...) of matrix_table.cpp:403-412): value rows that carry
+// the same row id are summed in fp32 in list order, then the updater steps
+// ONCE per distinct row on that row's weights and state. Rows not listed
+// are not touched.
+//
+// rows[n] holds local row ids with equal ids adjacent (no other order
+// needed); perm[j], when perm is non-null, is the row of vals that belongs
+// to rows[j], so a caller that sorted the ids need not reorder the payload.
+// Work item (j, c) = list position j, column-vector c, as in the kernels
+// above. An item whose id equals its predecessor's does nothing; a head
+// item walks its run of equal ids, sums vals[perm[k]][c] and hands the sum
+// to Op::step_at. Fixed summation order, no atomics, no LDS and no segment
+// table, so the result is reproducible and the host never syncs to learn
+// the number of distinct rows.
+//
+// Known limit: one thread group sums all occurrences of a row serially, so
+// a row listed thousands of times in one batch stretches the launch to the
+// length of that run. Splitting long runs is not done here.
+template <class Op, class V, class Idx>
+__global__ void k_row_update(Op op, const float* __restrict__ vals,
+                             const int64_t* __restrict__ rows,
+                             const int64_t* __restrict__ perm, int64_t n,
+                             Idx total, Idx cols) {
+  Idx stride = (Idx)gridDim.x * blockDim.x;
+  for (Idx i = (Idx)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += stride) {
+    Idx j = i / cols, c = i - j * cols;
+    int64_t r = rows[j];
+    if (j > 0 && rows[j - 1] == r) continue;
+    int64_t k = j;
+    V sum = ld<V>(vals, (perm ? perm[k] : k) * (int64_t)cols + c);
+    for (++k; k < n && rows[k] == r; ++k)
+      sum += ld<V>(vals, (perm ? perm[k] : k) * (int64_t)cols + c);
+    op.template step_at<V>(r * (int64_t)cols + c, sum);
+  }
+}
+
+static inline bool aligned16(const void* p) {
+  return ((uintptr_t)p & 15) == 0;
+}
+
+// `vec` (decided by the caller from cols % 4 and the 16-byte alignment of
+// every pointer the op and the kernel touch) selects V = v4f. Geometry is
+// the other row kernels' BLOCK x grid_for(total); no grid sweep has been
+// run for this shape. The 32-bit index form also needs room for the last
+// grid stride, so that i += stride cannot wrap.
+template <class Op>
+static void launch_row_update(const Op& op, bool vec, const float* vals,
+                              const int64_t* rows, const int64_t* perm,
+                              int64_t n, int64_t cols, hipStream_t s) {
+  if (!n || !cols) return;
+  int64_t vcols = vec ? cols / 4 : cols, total = n * vcols;
+  int grid = grid_for(total);
+  bool narrow = total <= (int64_t)UINT32_MAX - (int64_t)MAX_GRID * BLOCK;
+  if (vec && narrow)
+    k_row_update<Op, v4f, uint32_t><<<grid, BLOCK, 0, s>>>(
+        op, vals, rows, perm, n, (uint32_t)total, (uint32_t)vcols);
+  else if (vec)
+    k_row_update<Op, v4f, int64_t><<<grid, BLOCK, 0, s>>>(
+        op, vals, rows, perm, n, total, vcols);
+  else if (narrow)
+    k_row_update<Op, float, uint32_t><<<grid, BLOCK, 0, s>>>(
+        op, vals, rows, perm, n, (uint32_t)total, (uint32_t)vcols);
+  else
+    k_row_update<Op, float, int64_t><<<grid, BLOCK, 0, s>>>(
+        op, vals, rows, perm, n, total, vcols);
+}
+
 extern "C" {
+
+void mv_launch_row_momentum(float* shard, float* m, const float* vals,
+                            const int64_t* rows, const int64_t* perm,
+                            float mu, int64_t nrows, int64_t cols,
+                            hipStream_t s) {
+  bool vec = cols % 4 == 0 && aligned16(shard) && aligned16(m) &&
+             aligned16(vals);
+  launch_row_update(MomentumOp<float>{shard, m, nullptr, mu}, vec, vals, rows,
+                    perm, nrows, cols, s);
+}
+
+void mv_launch_row_dcasgd(float* shard, float* bak, const float* vals,
+                          const int64_t* rows, const int64_t* perm, float lr,
+                          float lambda, int64_t nrows, int64_t cols,
+                          hipStream_t s) {
+  bool vec = cols % 4 == 0 && aligned16(shard) && aligned16(bak) &&
+             aligned16(vals);
+  launch_row_update(DcasgdOp{shard, bak, nullptr, lr, lambda}, vec, vals,
+                    rows, perm, nrows, cols, s);
+}
+
+void mv_launch_row_dcasgda(float* shard, float* bak, float* msq,
+                           const float* vals, const int64_t* rows,
+                           const int64_t* perm, float lr, float lambda,
+                           float rho, float eps, int64_t nrows, int64_t cols,
+                           hipStream_t s) {
+  bool vec = cols % 4 == 0 && aligned16(shard) && aligned16(bak) &&
+             aligned16(msq) && aligned16(vals);
+  launch_row_update(DcasgdaOp{shard, bak, msq, nullptr, lr, lambda, rho, eps},
+                    vec, vals, rows, perm, nrows, cols, s);
+}
+
 
 void mv_launch_row_gather(float* out, const float* shard, const int64_t* rows,
                           int64_t nrows, int64_t cols, hipStream_t s) {

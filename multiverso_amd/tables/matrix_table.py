@@ -14,6 +14,11 @@ MI355X mapping:
   K5/K6 gather/scatter kernels on its HBM shard. This replaces the
   per-server Request_Get/Add message fan-out (matrix_table.cpp:235-314)
   with per-destination bucketed traffic matched to xGMI's 7 p2p links.
+- row-keyed Add runs the table's own updater on the touched rows only
+  (matrix_table.cpp:403-412): default/sgd scatter-add, adagrad the keyed
+  K15 kernel, momentum/dcasgd/dcasgda the k_row_update kernel — duplicate
+  ids of one batch are summed in batch order, then one updater step per
+  distinct row; weights and updater state of other rows stay as they are.
 
 Sparse/stale-aware Get (SparseMatrixTable's per-(worker,row) freshness
 bitmap) is implemented in sparse_matrix.py on top of this class.
@@ -220,7 +225,9 @@ class MatrixTable(Table):
         """K5 on the owned shard. default adds, sgd subtracts (the per-row
         updater dispatch of matrix_table.cpp:406-412); adagrad applies the
         keyed K15 form (duplicate rows: GPU races benignly via atomics,
-        CPU pre-aggregates duplicates — both keep the G accumulate)."""
+        CPU pre-aggregates duplicates — both keep the G accumulate);
+        momentum, dcasgd and dcasgda sum duplicate rows and step once per
+        distinct row (_row_update_stateful)."""
         from ..configure import get_flag
         if (get_flag("deterministic") and not assume_unique
                 and local_ids.numel()):
@@ -261,10 +268,12 @@ class MatrixTable(Table):
                                       torch.sqrt(gsq[urows]
                                                  + self.updater.EPS))
             return
+        if self.updater_type in ("momentum", "dcasgd", "dcasgda"):
+            self._row_update_stateful(local_ids, vals, option, assume_unique)
+            return
         sign = {"default": 1.0, "sgd": -1.0}.get(self.updater_type)
         CHECK(sign is not None,
-              f"row-keyed Add with updater '{self.updater_type}' is not "
-              "supported yet (stateful updaters need segmented row update)")
+              f"row-keyed Add: unknown updater '{self.updater_type}'")
         if self.shard.is_cuda and self.dtype == torch.float32:
             from .. import ops
             ops.module(required=True).row_scatter_add(
@@ -273,6 +282,71 @@ class MatrixTable(Table):
         else:
             self.shard.index_add_(0, local_ids,
                                   vals.view(-1, self.num_col) * sign)
+
+    def _row_update_stateful(self, local_ids: torch.Tensor,
+                             vals: torch.Tensor,
+                             option: Optional[AddOption],
+                             assume_unique: bool) -> None:
+        """Keyed momentum / dcasgd / dcasgda: value rows with the same id
+        are summed in batch order, then the updater steps once per distinct
+        row on that row's weights and state slices; rows not in the batch
+        keep both. ``option`` defaults as in the updater's whole-table
+        ``update``."""
+        if not local_ids.numel():
+            return
+        upd = self.updater
+        name = self.updater_type
+        shape = (self.local_rows, self.num_col)
+        vals2 = vals.reshape(-1, self.num_col)
+        if name == "momentum":
+            mu = float(option.momentum) if option else 0.0
+            m = upd.smooth_gradient.view(shape)
+        else:
+            opt = option or AddOption()
+            lr, lam = float(opt.learning_rate), float(opt.lambda_)
+            bak = upd._backup(opt.worker_id).view(shape)
+        if self.shard.is_cuda and self.dtype == torch.float32:
+            from .. import ops
+            hip = ops.module(required=True)
+            perm = None
+            if not assume_unique:
+                # equal ids adjacent, batch order kept inside each run; the
+                # kernel reads the payload through perm, so vals stay put
+                local_ids, perm = torch.sort(local_ids, stable=True)
+            vals2 = vals2.contiguous()
+            if name == "momentum":
+                hip.row_momentum_update(self.shard, m, local_ids, vals2, mu,
+                                        perm)
+            elif name == "dcasgd":
+                hip.row_dcasgd_update(self.shard, bak, local_ids, vals2, lr,
+                                      lam, perm)
+            else:
+                hip.row_dcasgda_update(self.shard, bak,
+                                       upd.mean_sqr.view(shape), local_ids,
+                                       vals2, lr, lam, float(opt.rho),
+                                       upd.EPS, perm)
+            return
+        # CPU and non-fp32 tables: the same semantics in torch ops
+        urows, inv = torch.unique(local_ids, return_inverse=True)
+        g = torch.zeros(urows.numel(), self.num_col, dtype=self.dtype,
+                        device=self.shard.device)
+        g.index_add_(0, inv, vals2)
+        if name == "momentum":
+            mm = m[urows].mul_(mu).add_(g, alpha=1.0 - mu)
+            m[urows] = mm
+            self.shard[urows] -= mm
+            return
+        w, b = self.shard[urows], bak[urows]
+        if name == "dcasgd":
+            w = w - lr * (g + lam * g * g * (w - b))
+        else:
+            msq = upd.mean_sqr.view(shape)
+            ms = msq[urows].mul_(opt.rho).add_((1.0 - opt.rho) * g * g)
+            msq[urows] = ms
+            lam_t = lam / torch.sqrt(ms + upd.EPS)
+            w = w - lr * (g + lam_t * g * g * (w - b))
+        self.shard[urows] = w
+        bak[urows] = w
 
     def get_rows(self, row_ids) -> torch.Tensor:
         """Row-subset Get: returns [len(row_ids), num_col] in caller order.

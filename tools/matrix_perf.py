@@ -4,12 +4,14 @@
 prints the Dashboard.
 
 Run (CPU or GPU):  python tools/matrix_perf.py [--rows N] [--cols N]
+                       [--updater momentum]   (times the keyed updater path)
 Multi-rank:        python -m torch.distributed.run --nproc-per-node N \
                        --master-addr 127.0.0.1 tools/matrix_perf.py
 """
 
 import argparse
 import os
+import statistics
 import sys
 import time
 
@@ -26,9 +28,30 @@ def main():
     p.add_argument("--sparse", action="store_true",
                    help="TestSparsePerf equivalent: SparseMatrixTable "
                         "stale-filtered get_into instead of dense get")
+    p.add_argument("--updater", default="default",
+                   choices=["default", "sgd", "momentum", "adagrad",
+                            "dcasgd", "dcasgda"],
+                   help="updater_type of the table; the keyed Adds carry a "
+                        "matching AddOption")
+    p.add_argument("--repeat", type=int, default=1,
+                   help="time each keyed Add this many times after one "
+                        "untimed warm-up and print the median (1: a single "
+                        "cold timing)")
+    p.add_argument("--seed", type=int, default=None,
+                   help="seed the row choice, to time the same ids twice")
+    p.add_argument("--torch-composed", action="store_true",
+                   help="with --updater momentum on one rank: replace the "
+                        "keyed Add by its composition from torch ops "
+                        "(unique + index_add_ + indexed formula) on the "
+                        "table's own shard and state, as a baseline")
     args = p.parse_args()
+    if args.torch_composed and (args.updater != "momentum" or args.sparse):
+        p.error("--torch-composed needs --updater momentum without --sparse")
+    if args.seed is not None:
+        torch.manual_seed(args.seed)
 
     import multiverso_amd as mv
+    from multiverso_amd.log import CHECK
     mv.init(sync=True)
     device = mv.Zoo.get().device
     if device.type != "cuda":
@@ -36,9 +59,15 @@ def main():
 
     if args.sparse:
         t = mv.SparseMatrixTable(args.rows, args.cols,
-                                 updater_type="default")
+                                 updater_type=args.updater)
     else:
-        t = mv.MatrixTable(args.rows, args.cols, updater_type="default")
+        t = mv.MatrixTable(args.rows, args.cols, updater_type=args.updater)
+    option = None
+    if args.updater == "momentum":
+        option = mv.AddOption(momentum=0.9)
+    elif args.updater in ("adagrad", "dcasgd", "dcasgda"):
+        option = mv.AddOption(worker_id=mv.rank(), learning_rate=0.1,
+                              rho=0.1, lambda_=0.1)
     out = torch.empty(args.rows, args.cols, device=device)
 
     def timed(fn):
@@ -51,6 +80,27 @@ def main():
             torch.cuda.synchronize()
         mv.barrier()
         return (time.perf_counter() - t0) * 1e3
+
+    def composed_add(ids, vals):
+        mu = option.momentum
+        w, m = t.shard, t.updater.smooth_gradient.view_as(t.shard)
+        urows, inv = torch.unique(ids, return_inverse=True)
+        agg = torch.zeros(urows.numel(), args.cols, device=device)
+        agg.index_add_(0, inv, vals)
+        mm = m[urows] * mu + (1.0 - mu) * agg
+        m[urows] = mm
+        w[urows] -= mm
+
+    def timed_add(ids, vals):
+        if args.torch_composed:
+            CHECK(mv.size() == 1, "--torch-composed runs on one rank")
+            fn = lambda: composed_add(ids, vals)
+        else:
+            fn = lambda: t.add_rows(ids, vals, option)
+        if args.repeat <= 1:
+            return timed(fn)
+        timed(fn)
+        return statistics.median(timed(fn) for _ in range(args.repeat))
 
     rows_all = torch.arange(args.rows, device=device)
     results = []
@@ -66,7 +116,7 @@ def main():
 
             get_before = timed(sget)
             n_before = got[0]
-            add_ms = timed(lambda: t.add_rows(ids, vals))
+            add_ms = timed_add(ids, vals)
             get_after = timed(sget)
             results.append((pct, add_ms, get_before, get_after))
             if mv.rank() == 0:
@@ -76,7 +126,7 @@ def main():
                       f"({got[0]} rows)", flush=True)
         else:
             get_before = timed(lambda: t.get(out=out))
-            add_ms = timed(lambda: t.add_rows(ids, vals))
+            add_ms = timed_add(ids, vals)
             get_after = timed(lambda: t.get(out=out))
             results.append((pct, add_ms, get_before, get_after))
             if mv.rank() == 0:
