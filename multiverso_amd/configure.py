@@ -93,7 +93,7 @@ def _define_core_flags() -> None:
     define_flag("ma", False, "model-average mode (reference zoo.cpp:24): aggregate() is always available here; the flag is accepted so reference launch lines work unchanged")
     define_flag("sync", False, "BSP synchronous server (vector-clocked)")
     define_flag("backup_worker_ratio", 0.0, "vestigial in reference; kept for parity")
-    define_flag("updater_type", "default", "default|sgd|momentum|adagrad")
+    define_flag("updater_type", "default", "default|sgd|momentum|adagrad|dcasgd|dcasgda|adam")
     define_flag("omp_threads", 0, "CPU-fallback intra-op threads (reference updater.cpp:18; 0 = torch default)")
     define_flag("allocator_type", "smart", "kept for parity; caching allocator is torch's")
     define_flag("allocator_alignment", 16, "kept for parity")

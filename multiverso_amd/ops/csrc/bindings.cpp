@@ -32,6 +32,14 @@ void mv_launch_dcasgd(float*, float*, const float*, float*, float, float,
                       int64_t, hipStream_t);
 void mv_launch_dcasgda(float*, float*, float*, const float*, float*, float,
                        float, float, float, int64_t, hipStream_t);
+// adam: (..., b1, b2, step = lr/(1-b1^t), rbc2 = 1/sqrt(1-b2^t),
+// decay = 1-lr*wd, eps, n), all scalars in double
+void mv_launch_adam(float*, float*, float*, const float*, float*, double,
+                    double, double, double, double, double, int64_t,
+                    hipStream_t);
+void mv_launch_adam_f64(double*, double*, double*, const double*, double,
+                        double, double, double, double, double, int64_t,
+                        hipStream_t);
 void mv_launch_row_gather(float*, const float*, const int64_t*, int64_t,
                           int64_t, hipStream_t);
 void mv_launch_row_scatter_add(float*, const float*, const int64_t*, float,
@@ -63,6 +71,9 @@ void mv_launch_row_dcasgd(float*, float*, const float*, const int64_t*,
 void mv_launch_row_dcasgda(float*, float*, float*, const float*,
                            const int64_t*, const int64_t*, float, float,
                            float, float, int64_t, int64_t, hipStream_t);
+void mv_launch_row_adam(float*, float*, float*, const float*, const int64_t*,
+                        const int64_t*, double, double, double, double,
+                        double, double, int64_t, int64_t, hipStream_t);
 void mv_launch_lr_softmax_fwd(const float*, const int64_t*, const float*,
                               const int*, const float*, const float*,
                               float*, float*, int64_t, int64_t, hipStream_t);
@@ -255,6 +266,34 @@ void dcasgda_copy_update(torch::Tensor data, torch::Tensor bak,
                     cur_stream());
 }
 
+// step = lr / (1 - b1^t), rbc2 = 1 / sqrt(1 - b2^t), decay = 1 - lr*wd:
+// the caller owns the update count t
+void adam_update(torch::Tensor data, torch::Tensor m, torch::Tensor v,
+                 torch::Tensor delta, double b1, double b2, double step,
+                 double rbc2, double decay, double eps) {
+  auto st = data.scalar_type();
+  int64_t n = check_same({{"data", data}, {"m", m}, {"v", v},
+                          {"delta", delta}}, st);
+  if (st == torch::kFloat32)
+    mv_launch_adam(f32(data), f32(m), f32(v), f32(delta), nullptr, b1, b2,
+                   step, rbc2, decay, eps, n, cur_stream());
+  else if (st == torch::kFloat64)
+    mv_launch_adam_f64(f64(data), f64(m), f64(v), f64(delta), b1, b2, step,
+                       rbc2, decay, eps, n, cur_stream());
+  else
+    TORCH_CHECK(false, "adam_update: unsupported dtype ", data.dtype());
+}
+
+void adam_copy_update(torch::Tensor data, torch::Tensor m, torch::Tensor v,
+                      torch::Tensor delta, torch::Tensor out, double b1,
+                      double b2, double step, double rbc2, double decay,
+                      double eps) {
+  int64_t n = check_same({{"data", data}, {"m", m}, {"v", v},
+                          {"delta", delta}, {"out", out}});
+  mv_launch_adam(f32(data), f32(m), f32(v), f32(delta), f32(out), b1, b2,
+                 step, rbc2, decay, eps, n, cur_stream());
+}
+
 torch::Tensor row_gather(torch::Tensor shard, torch::Tensor rows) {
   check_f32(shard, "shard");
   TORCH_CHECK(shard.dim() == 2, "shard must be 2-D");
@@ -363,6 +402,17 @@ void row_dcasgda_update(torch::Tensor shard, torch::Tensor bak,
                         rows.data_ptr<int64_t>(), pp, (float)lr,
                         (float)lambda, (float)rho, (float)eps, rows.numel(),
                         shard.size(1), cur_stream());
+}
+
+void row_adam_update(torch::Tensor shard, torch::Tensor m, torch::Tensor v,
+                     torch::Tensor rows, torch::Tensor vals, double b1,
+                     double b2, double step, double rbc2, double decay,
+                     double eps, c10::optional<torch::Tensor> perm) {
+  const int64_t* pp = check_row_update(shard, {{"m", m}, {"v", v}}, rows,
+                                       vals, perm);
+  mv_launch_row_adam(f32(shard), f32(m), f32(v), f32(vals),
+                     rows.data_ptr<int64_t>(), pp, b1, b2, step, rbc2, decay,
+                     eps, rows.numel(), shard.size(1), cur_stream());
 }
 
 void w2v_train(torch::Tensor in_emb, torch::Tensor out_emb,
@@ -644,6 +694,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "DC-ASGD: delay-compensated update with per-worker backup");
   m.def("dcasgda_update", &dcasgda_update,
         "DC-ASGD-a: adaptive lambda via mean-square of gradients");
+  m.def("adam_update", &adam_update,
+        "fused Adam/AdamW step (fp32, fp64); step = lr/(1-b1^t), "
+        "rbc2 = 1/sqrt(1-b2^t), decay = 1-lr*wd",
+        py::arg("data"), py::arg("m"), py::arg("v"), py::arg("delta"),
+        py::arg("b1"), py::arg("b2"), py::arg("step"), py::arg("rbc2"),
+        py::arg("decay"), py::arg("eps"));
+  m.def("adam_copy_update", &adam_copy_update, "fused adam Add+Get",
+        py::arg("data"), py::arg("m"), py::arg("v"), py::arg("delta"),
+        py::arg("out"), py::arg("b1"), py::arg("b2"), py::arg("step"),
+        py::arg("rbc2"), py::arg("decay"), py::arg("eps"));
   m.def("row_gather", &row_gather, "K6: out[i] = shard[rows[i]]");
   m.def("row_gather_out", &row_gather_out, "K6 (preallocated out)");
   m.def("row_scatter_add", &row_scatter_add,
@@ -696,6 +756,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("shard"), py::arg("bak"), py::arg("msq"), py::arg("rows"),
         py::arg("vals"), py::arg("lr"), py::arg("lam"), py::arg("rho"),
         py::arg("eps"), py::arg("perm") = py::none());
+  m.def("row_adam_update", &row_adam_update,
+        "keyed Adam, same row/perm contract as row_momentum_update",
+        py::arg("shard"), py::arg("m"), py::arg("v"), py::arg("rows"),
+        py::arg("vals"), py::arg("b1"), py::arg("b2"), py::arg("step"),
+        py::arg("rbc2"), py::arg("decay"), py::arg("eps"),
+        py::arg("perm") = py::none());
   m.def("w2v_train", &w2v_train,
         "K9-K11: fused word2vec block training (skip-gram/CBOW, NS/HS, "
         "optional adagrad)");

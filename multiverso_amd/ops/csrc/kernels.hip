@@ -14,8 +14,8 @@
 // plain copy and the f64/int forms, COPY_BLOCK = 1024 threads x
 // COPY_GRID = 768 blocks for the fused Add+Get bodies; MAX_GRID = 2048
 // (256 CUs x 8 blocks) only caps the row-keyed, word2vec and logreg
-// kernels. The stateful updaters (momentum/adagrad/dcasgd) fuse the state
-// read-modify-write into the same pass as the weight update — one trip
+// kernels. The stateful updaters (momentum/adagrad/dcasgd/adam) fuse the
+// state read-modify-write into the same pass as the weight update — one trip
 // through HBM3E instead of the 3-4 separate passes a torch-op composition
 // would make.
 //
@@ -107,9 +107,10 @@ static inline int grid_for(int64_t work_items) {
 // updater.cpp:40-43) run the same ops with V = T, plain scalar access.
 // Every step issues all its loads before its first store: struct members
 // carry no __restrict__, so a load written after a store would wait for it.
-// The momentum and DC-ASGD ops keep their formula in step_at<V>(i, g), which
-// takes the gradient as a value (step loads it from delta first): the
-// row-keyed k_row_update below hands it a per-row sum instead.
+// The momentum, DC-ASGD and Adam ops keep their formula in
+// step_at<V>(i, g), which takes the gradient as a value (step loads it from
+// delta first): the row-keyed k_row_update below hands it a per-row sum
+// instead.
 // ---------------------------------------------------------------------------
 
 template <class T>
@@ -220,6 +221,53 @@ struct DcasgdaOp {
     return step_at<V>(i, ld<V>(delta, i));
   }
 };
+
+// Adam / AdamW ("adam"; not in the reference's set, semantics as
+// torch.optim.Adam/AdamW with amsgrad off, SparseAdam for keyed batches):
+//   w  = w * decay                         decay = 1 - lr*wd (1 is plain Adam)
+//   m  = b1*m + (1-b1)*g
+//   v  = b2*v + (1-b2)*g*g
+//   w -= alpha * m / (sqrt(v) * rbc2 + eps)
+// alpha = lr / (1 - b1^t) and rbc2 = 1 / sqrt(1 - b2^t) are the bias
+// corrections for the shard's update count t; the host computes them, and
+// decay, in double, so the kernel keeps no step state. One pass at
+// 28 B/element (fp32): read w, m, v, g; write w, m, v. The pass is
+// memory-bound, so sqrt and the divide are the correctly rounded ones (not
+// the rsq helper). Every multiply-add that could contract is an explicit
+// fma, as in MomentumOp: the v4f body, the scalar tail and k_row_update
+// must round alike.
+template <class T>
+struct AdamOp {
+  using elem = T;
+  T* data; T* m; T* v; const T* delta;
+  T b1, omb1, b2, omb2, alpha, rbc2, decay, eps;
+  template <class V> __device__ __forceinline__ V step_at(int64_t i,
+                                                          V g) const {
+    V w = ld<V>(data, i), mm = ld<V>(m, i), vv = ld<V>(v, i);
+    mm = __builtin_elementwise_fma((V)b1, mm, omb1 * g);
+    vv = __builtin_elementwise_fma((V)b2, vv, omb2 * g * g);
+    V den = __builtin_elementwise_fma(__builtin_elementwise_sqrt(vv), (V)rbc2,
+                                      (V)eps);
+    w = __builtin_elementwise_fma((V)(-alpha), mm / den, w * decay);
+    st(m, i, mm);
+    st(v, i, vv);
+    st(data, i, w);
+    return w;
+  }
+  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+    return step_at<V>(i, ld<V>(delta, i));
+  }
+};
+
+// Adam's scalars arrive in double (the host's bias corrections and decay
+// factor) and are rounded to the table's type once, here.
+template <class T>
+static AdamOp<T> adam_op(T* data, T* m, T* v, const T* delta, double b1,
+                         double b2, double step, double rbc2, double decay,
+                         double eps) {
+  return AdamOp<T>{data, m, v, delta, (T)b1, (T)(1.0 - b1), (T)b2,
+                   (T)(1.0 - b2), (T)step, (T)rbc2, (T)decay, (T)eps};
+}
 
 // K7 Access / shard copy-out: non-temporal streaming copy.
 struct CopyOp {
@@ -341,6 +389,23 @@ void mv_launch_dcasgda(float* data, float* bak, float* msq, const float* delta,
                 n, STATE_GRID, s);
 }
 
+// Geometry is the other stateful updaters' STATE_GRID (COPY_BLOCK x
+// COPY_GRID with `out`): no grid sweep has been run for a 4-read/3-write
+// stream.
+void mv_launch_adam(float* data, float* m, float* v, const float* delta,
+                    float* out, double b1, double b2, double step,
+                    double rbc2, double decay, double eps, int64_t n,
+                    hipStream_t s) {
+  launch_update(adam_op(data, m, v, delta, b1, b2, step, rbc2, decay, eps),
+                out, n, STATE_GRID, s);
+}
+void mv_launch_adam_f64(double* d, double* m, double* v, const double* x,
+                        double b1, double b2, double step, double rbc2,
+                        double decay, double eps, int64_t n, hipStream_t s) {
+  launch_elem<false>(adam_op(d, m, v, x, b1, b2, step, rbc2, decay, eps),
+                     nullptr, n, STATE_GRID, BLOCK, s);
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
@@ -420,7 +485,7 @@ __global__ void k_row_scatter_adagrad(float* __restrict__ shard,
   }
 }
 
-// Keyed stateful update (momentum, dcasgd, dcasgda; the per-row
+// Keyed stateful update (momentum, dcasgd, dcasgda, adam; the per-row
 // updater_->Update(...) of matrix_table.cpp:403-412): value rows that carry
 // the same row id are summed in fp32 in list order, then the updater steps
 // ONCE per distinct row on that row's weights and state. Rows not listed
@@ -522,6 +587,17 @@ void mv_launch_row_dcasgda(float* shard, float* bak, float* msq,
                     vec, vals, rows, perm, nrows, cols, s);
 }
 
+void mv_launch_row_adam(float* shard, float* m, float* v, const float* vals,
+                        const int64_t* rows, const int64_t* perm, double b1,
+                        double b2, double step, double rbc2, double decay,
+                        double eps, int64_t nrows, int64_t cols,
+                        hipStream_t s) {
+  bool vec = cols % 4 == 0 && aligned16(shard) && aligned16(m) &&
+             aligned16(v) && aligned16(vals);
+  launch_row_update(adam_op<float>(shard, m, v, nullptr, b1, b2, step, rbc2,
+                                   decay, eps),
+                    vec, vals, rows, perm, nrows, cols, s);
+}
 
 void mv_launch_row_gather(float* out, const float* shard, const int64_t* rows,
                           int64_t nrows, int64_t cols, hipStream_t s) {

@@ -16,9 +16,10 @@ MI355X mapping:
   with per-destination bucketed traffic matched to xGMI's 7 p2p links.
 - row-keyed Add runs the table's own updater on the touched rows only
   (matrix_table.cpp:403-412): default/sgd scatter-add, adagrad the keyed
-  K15 kernel, momentum/dcasgd/dcasgda the k_row_update kernel — duplicate
-  ids of one batch are summed in batch order, then one updater step per
-  distinct row; weights and updater state of other rows stay as they are.
+  K15 kernel, momentum/dcasgd/dcasgda/adam the k_row_update kernel —
+  duplicate ids of one batch are summed in batch order, then one updater
+  step per distinct row; weights and updater state of other rows stay as
+  they are.
 
 Sparse/stale-aware Get (SparseMatrixTable's per-(worker,row) freshness
 bitmap) is implemented in sparse_matrix.py on top of this class.
@@ -226,8 +227,8 @@ class MatrixTable(Table):
         updater dispatch of matrix_table.cpp:406-412); adagrad applies the
         keyed K15 form (duplicate rows: GPU races benignly via atomics,
         CPU pre-aggregates duplicates — both keep the G accumulate);
-        momentum, dcasgd and dcasgda sum duplicate rows and step once per
-        distinct row (_row_update_stateful)."""
+        momentum, dcasgd, dcasgda and adam sum duplicate rows and step once
+        per distinct row (_row_update_stateful)."""
         from ..configure import get_flag
         if (get_flag("deterministic") and not assume_unique
                 and local_ids.numel()):
@@ -268,7 +269,7 @@ class MatrixTable(Table):
                                       torch.sqrt(gsq[urows]
                                                  + self.updater.EPS))
             return
-        if self.updater_type in ("momentum", "dcasgd", "dcasgda"):
+        if self.updater_type in ("momentum", "dcasgd", "dcasgda", "adam"):
             self._row_update_stateful(local_ids, vals, option, assume_unique)
             return
         sign = {"default": 1.0, "sgd": -1.0}.get(self.updater_type)
@@ -287,11 +288,12 @@ class MatrixTable(Table):
                              vals: torch.Tensor,
                              option: Optional[AddOption],
                              assume_unique: bool) -> None:
-        """Keyed momentum / dcasgd / dcasgda: value rows with the same id
-        are summed in batch order, then the updater steps once per distinct
-        row on that row's weights and state slices; rows not in the batch
-        keep both. ``option`` defaults as in the updater's whole-table
-        ``update``."""
+        """Keyed momentum / dcasgd / dcasgda / adam: value rows with the
+        same id are summed in batch order, then the updater steps once per
+        distinct row on that row's weights and state slices; rows not in the
+        batch keep both (adam does not decay them either). ``option``
+        defaults as in the updater's whole-table ``update``. A batch that
+        brings this shard no rows is no update: adam's count stays."""
         if not local_ids.numel():
             return
         upd = self.updater
@@ -301,6 +303,9 @@ class MatrixTable(Table):
         if name == "momentum":
             mu = float(option.momentum) if option else 0.0
             m = upd.smooth_gradient.view(shape)
+        elif name == "adam":
+            m, v = upd.exp_avg.view(shape), upd.exp_avg_sq.view(shape)
+            scalars = upd.next_scalars(option)
         else:
             opt = option or AddOption()
             lr, lam = float(opt.learning_rate), float(opt.lambda_)
@@ -317,6 +322,9 @@ class MatrixTable(Table):
             if name == "momentum":
                 hip.row_momentum_update(self.shard, m, local_ids, vals2, mu,
                                         perm)
+            elif name == "adam":
+                hip.row_adam_update(self.shard, m, v, local_ids, vals2,
+                                    *scalars, perm)
             elif name == "dcasgd":
                 hip.row_dcasgd_update(self.shard, bak, local_ids, vals2, lr,
                                       lam, perm)
@@ -335,6 +343,11 @@ class MatrixTable(Table):
             mm = m[urows].mul_(mu).add_(g, alpha=1.0 - mu)
             m[urows] = mm
             self.shard[urows] -= mm
+            return
+        if name == "adam":
+            w, mm, vv = self.shard[urows], m[urows], v[urows]
+            upd.torch_step(w, mm, vv, g, scalars)
+            self.shard[urows], m[urows], v[urows] = w, mm, vv
             return
         w, b = self.shard[urows], bak[urows]
         if name == "dcasgd":

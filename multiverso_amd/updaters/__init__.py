@@ -19,8 +19,20 @@ Capability parity with the reference updater family (selected by the
            from a submodule absent in the snapshot; math from Zheng et
            al., ICML 2017) with per-worker backup rows.
 
+One updater goes beyond the reference's set:
+
+- adam:    Adam / AdamW as in ``torch.optim`` (``SparseAdam`` for keyed
+           Adds): first and second moment per element, ONE update count
+           per shard on the host, bias corrections passed to the kernel as
+           scalars (``AdamUpdater``). float32 and float64 tables.
+
 ``AddOption`` keeps the reference's 20-byte wire envelope
-(include/multiverso/updater/updater.h:10-70) for C-API parity.
+(include/multiverso/updater/updater.h:10-70) for C-API parity; adam's
+hyperparameters ride in the same five fields (``AddOption.adam``).
+
+Updater state (momentum, accumulators, backups, Adam's moments and count)
+lives with the updater and is NOT written by a table's ``store`` or by
+``checkpoint``: a restored table resumes with fresh state.
 
 Each updater's ``update`` is ONE pass over the shard: on GPU it dispatches
 to the in-tree HIP extension (multiverso_amd.ops) — fused read-modify-write
@@ -62,6 +74,15 @@ class AddOption:
     def from_bytes(cls, b: bytes) -> "AddOption":
         w, m, lr, rho, lam = struct.unpack("<iffff", b[:20])
         return cls(w, m, lr, rho, lam)
+
+    @classmethod
+    def adam(cls, lr: float = 1e-3, beta1: float = 0.9,
+             beta2: float = 0.999, weight_decay: float = 0.0,
+             worker_id: int = 0) -> "AddOption":
+        """The option of an "adam" table. The envelope stays at five fields:
+        lr rides in ``learning_rate``, beta1 in ``momentum``, beta2 in
+        ``rho`` and the decoupled weight decay in ``lambda_``."""
+        return cls(worker_id, beta1, lr, beta2, weight_decay)
 
 
 def _hip_ops():
@@ -267,6 +288,83 @@ class DCASGDAUpdater(DCASGDUpdater):
             out.copy_(self.shard)
 
 
+class AdamUpdater(Updater):
+    """Adam / AdamW ("adam"), the first updater beyond the reference's set:
+
+        w  = w * (1 - lr*wd)              # decoupled decay; wd = 0: plain Adam
+        m  = b1*m + (1-b1)*g
+        v  = b2*v + (1-b2)*g*g
+        w -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+
+    i.e. ``torch.optim.Adam`` / ``AdamW`` with ``amsgrad=False``, and
+    ``SparseAdam`` for keyed batches. ``g`` is the delta as it reaches the
+    shard, unscaled (in the collective plane: the sum over workers).
+    ``step`` is ONE host-side count per shard of the updates applied so far,
+    whole-table and keyed alike; ``t`` is its value after the update, and
+    the bias corrections and the decay factor are computed from it on the
+    host in double and handed to the kernel as scalars. There is no per-row
+    count: a row that a keyed Add names rarely is corrected with the shard's
+    ``t``, as in ``SparseAdam``.
+
+    The 20-byte envelope carries the hyperparameters as ``learning_rate``
+    -> lr, ``momentum`` -> b1, ``rho`` -> b2, ``lambda_`` -> wd (see
+    ``AddOption.adam``); ``option=None`` means ``AddOption.adam()``, not the
+    ``AddOption()`` field defaults. float32 and float64 shards only."""
+
+    name = "adam"
+    EPS = 1e-8
+
+    def __init__(self, shard: torch.Tensor) -> None:
+        if shard.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"updater_type 'adam' needs a float32 or float64 "
+                            f"table, got {shard.dtype} (integer tables are "
+                            f"add-only: use 'default')")
+        super().__init__(shard)
+        self.exp_avg = torch.zeros_like(shard)
+        self.exp_avg_sq = torch.zeros_like(shard)
+        self.step = 0
+
+    def next_scalars(self, option: Optional[AddOption]):
+        """Count one update and return the kernel's scalars for it, all in
+        double: (b1, b2, lr/(1-b1^t), 1/sqrt(1-b2^t), 1-lr*wd, eps)."""
+        opt = option if option is not None else AddOption.adam()
+        lr, b1 = float(opt.learning_rate), float(opt.momentum)
+        b2, wd = float(opt.rho), float(opt.lambda_)
+        self.step += 1
+        t = self.step
+        return (b1, b2, lr / (1.0 - b1 ** t), (1.0 - b2 ** t) ** -0.5,
+                1.0 - lr * wd, self.EPS)
+
+    @staticmethod
+    def torch_step(w: torch.Tensor, m: torch.Tensor, v: torch.Tensor,
+                   g: torch.Tensor, scalars) -> None:
+        """The same formula in torch ops, in place on w, m and v (CPU, and
+        the keyed path of tables the row kernel does not cover)."""
+        b1, b2, step, rbc2, decay, eps = scalars
+        w.mul_(decay)
+        m.mul_(b1).add_(g, alpha=1.0 - b1)
+        v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
+        w.addcdiv_(m, v.sqrt().mul_(rbc2).add_(eps), value=-step)
+
+    def update(self, delta: torch.Tensor, option: Optional[AddOption]) -> None:
+        s = self.next_scalars(option)
+        if self.shard.is_cuda:
+            _hip_ops().adam_update(self.shard, self.exp_avg, self.exp_avg_sq,
+                                   delta, *s)
+        else:
+            self.torch_step(self.shard, self.exp_avg, self.exp_avg_sq, delta,
+                            s)
+
+    def update_and_copy(self, delta, option, out) -> None:
+        if self.shard.is_cuda and self.shard.dtype == torch.float32:
+            _hip_ops().adam_copy_update(self.shard, self.exp_avg,
+                                        self.exp_avg_sq, delta, out,
+                                        *self.next_scalars(option))
+        else:
+            self.update(delta, option)
+            out.copy_(self.shard)
+
+
 _REGISTRY: Dict[str, Type[Updater]] = {
     "default": Updater,
     "sgd": SGDUpdater,
@@ -274,6 +372,7 @@ _REGISTRY: Dict[str, Type[Updater]] = {
     "adagrad": AdaGradUpdater,
     "dcasgd": DCASGDUpdater,
     "dcasgda": DCASGDAUpdater,
+    "adam": AdamUpdater,
 }
 
 

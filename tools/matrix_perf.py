@@ -30,7 +30,7 @@ def main():
                         "stale-filtered get_into instead of dense get")
     p.add_argument("--updater", default="default",
                    choices=["default", "sgd", "momentum", "adagrad",
-                            "dcasgd", "dcasgda"],
+                            "dcasgd", "dcasgda", "adam"],
                    help="updater_type of the table; the keyed Adds carry a "
                         "matching AddOption")
     p.add_argument("--repeat", type=int, default=1,
@@ -68,6 +68,9 @@ def main():
     elif args.updater in ("adagrad", "dcasgd", "dcasgda"):
         option = mv.AddOption(worker_id=mv.rank(), learning_rate=0.1,
                               rho=0.1, lambda_=0.1)
+    elif args.updater == "adam":
+        option = mv.AddOption.adam(lr=0.1, weight_decay=0.01,
+                                   worker_id=mv.rank())
     out = torch.empty(args.rows, args.cols, device=device)
 
     def timed(fn):
