@@ -118,6 +118,8 @@ class AsyncEngine:
     # docs/ENGINEERING_NOTES.md — so an Add is 2 messages, not 3-4).
     # Blob layout, 8-byte aligned by construction:
     #   [opt: 5 f64 if has_opt][keys: n_keys i64][vals: n_vals dtype]
+    # Value payloads, of requests and replies alike, are in the table's wire
+    # dtype (table.wire: the table's dtype, or bf16 on a bf16-wire table).
     def _send_request(self, dst: int, hdr_fields: List[int],
                       payloads: List[torch.Tensor]):
         """Returns (works, refs): pending isends + the buffers that must
@@ -182,7 +184,7 @@ class AsyncEngine:
             w, r = self._send_request(dst, hdr, [])
             works += w
             refs += r
-            buf = torch.empty(cnt * unit, dtype=table.dtype)
+            buf = torch.empty(cnt * unit, dtype=table.wire)
             works.append(dist.irecv(buf, dst, group=self.rep))
             slots.append((buf, dst_slice))
             refs.append(buf)
@@ -239,7 +241,7 @@ class AsyncEngine:
         zoo = self.zoo
         order, counts = self._plan_keyed(table, ids_cpu)
         sorted_ids = ids_cpu[order]
-        out = torch.empty(ids_cpu.numel(), unit, dtype=table.dtype,
+        out = torch.empty(ids_cpu.numel(), unit, dtype=table.wire,
                           device=table.device)
         works: List = []
         refs: List = []
@@ -263,7 +265,7 @@ class AsyncEngine:
             w, r = self._send_request(dst, hdr, [kcpu])
             works += w
             refs += r
-            buf = torch.empty(cnt * unit, dtype=table.dtype)
+            buf = torch.empty(cnt * unit, dtype=table.wire)
             works.append(dist.irecv(buf, dst, group=self.rep))
             slots.append((buf, rows))
             refs.append(buf)
@@ -461,7 +463,7 @@ class AsyncEngine:
         # _send_request: [opt][keys][vals], 8-byte aligned sections)
         vals_dtype = None
         if n_vals and op in (OP_ADD, OP_ADD_ROWS):
-            vals_dtype = table.dtype
+            vals_dtype = table.wire
         elif n_vals and op == OP_KV_ADD:
             vals_dtype = torch.float64
         vals_bytes = (0 if vals_dtype is None
@@ -492,7 +494,9 @@ class AsyncEngine:
                           group=self.rep)
         elif op == OP_GET:
             with monitor("server.process_get"):
-                out = torch.empty(n_vals, dtype=table.dtype)
+                # a bf16-wire shard is narrowed on the GPU first, so the
+                # D2H copy is half size too
+                out = torch.empty(n_vals, dtype=table.wire)
                 table._server_read_chunk_into(out)
             dist.send(out, src, group=self.rep)
         elif op == OP_ADD_ROWS:

@@ -14,6 +14,11 @@ MI355X-native mapping (BASELINE.json north star):
   p2p traffic is batched per destination, which matches xGMI's 7
   point-to-point links far better than a ring of small messages
 - aggregate (MV_Aggregate / -ma mode) = one all-reduce
+- bf16 wire format (tables built with ``wire_dtype=torch.bfloat16``): the
+  same collectives carry bfloat16 payloads for an fp32 shard. Nothing here is
+  dtype-specific except the Get side, where the owner narrows its shard
+  before the all-gather (``narrow_shard``). A reduce-scatter of bf16 deltas
+  sums in bf16, with the backend's rounding.
 
 Sharding parity: contiguous partition with ``total // n`` per server and
 the remainder on the last server — identical to ArrayTable
@@ -122,6 +127,25 @@ def exchange_size_rows(rows: List[List[int]]) -> List[List[int]]:
     return [[flat[d * k + i] for d in range(n)] for i in range(k)]
 
 
+def narrow_shard(shard_flat: torch.Tensor, dtype: torch.dtype,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``shard_flat`` cast to ``dtype``, into ``out`` when given. An fp32
+    shard going to bf16 (the bf16 wire, round to nearest even) takes the K7
+    narrowing copy on GPU, which agrees bit for bit with torch's cast; every
+    other pair, and the CPU, is torch's ``copy_``."""
+    if out is None:
+        out = torch.empty(shard_flat.numel(), dtype=dtype,
+                          device=shard_flat.device)
+    if (shard_flat.dtype == torch.float32 and out.dtype == torch.bfloat16
+            and shard_flat.is_cuda and out.device == shard_flat.device
+            and out.is_contiguous() and shard_flat.is_contiguous()):
+        from . import ops
+        ops.module(required=True).nt_copy(out, shard_flat)
+    else:
+        out.copy_(shard_flat)
+    return out
+
+
 def allgather_shards(out_flat: torch.Tensor, shard_flat: torch.Tensor,
                      spec: ShardSpec, unit: int, async_op: bool = False) -> Handle:
     """Gather every server's shard into ``out_flat`` (size total*unit).
@@ -129,11 +153,18 @@ def allgather_shards(out_flat: torch.Tensor, shard_flat: torch.Tensor,
     ``unit`` = elements per shard unit (row width for matrices, 1 for
     arrays). Fast path (even shards): one all_gather_into_tensor straight
     into the user buffer — zero staging copies. Uneven: padded gather.
+    A bf16 ``out_flat`` over an fp32 shard is the bf16 wire format: the
+    owner narrows, the gather carries bf16 (single rank: the narrowing copy
+    writes straight into ``out_flat``).
     """
+    narrowing = (out_flat.dtype == torch.bfloat16
+                 and shard_flat.dtype == torch.float32)
     if not _dist():
         off, cnt = spec.range_of(0)
         dst = out_flat[off * unit:(off + cnt) * unit]
-        if (dst.is_cuda and dst.dtype == torch.float32
+        if narrowing:
+            narrow_shard(shard_flat, dst.dtype, out=dst)
+        elif (dst.is_cuda and dst.dtype == torch.float32
                 and dst.is_contiguous() and shard_flat.is_contiguous()):
             from . import ops
             m = ops.module(required=True)
@@ -141,6 +172,8 @@ def allgather_shards(out_flat: torch.Tensor, shard_flat: torch.Tensor,
         else:
             dst.copy_(shard_flat)
         return _NOOP
+    if narrowing:
+        shard_flat = narrow_shard(shard_flat, out_flat.dtype)
     if spec.even and out_flat.is_contiguous():
         work = dist.all_gather_into_tensor(out_flat, shard_flat, async_op=async_op)
         return Handle(work) if async_op else _NOOP

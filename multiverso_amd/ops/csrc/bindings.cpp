@@ -10,39 +10,42 @@
 #include <cstdint>
 
 extern "C" {
-// elementwise updaters: a non-null `out` (the float* before the scalars)
-// selects the fused Add+Get form
-void mv_launch_copy(float*, const float*, int64_t, hipStream_t);
-void mv_launch_add(float*, const float*, int64_t, hipStream_t);
+// elementwise updaters: a non-null `out` (the pointer before `wire`)
+// selects the fused Add+Get form. The fp32 forms take the delta and `out`
+// as void* and, in `wire`, the WIRE_* bits that say which holds bf16.
+void mv_launch_copy(void*, const float*, int, int64_t, hipStream_t);
+void mv_launch_add(float*, const void*, int, int64_t, hipStream_t);
 void mv_launch_add_f64(double*, const double*, int64_t, hipStream_t);
 void mv_launch_add_i32(int32_t*, const int32_t*, int64_t, hipStream_t);
 void mv_launch_add_i64(int64_t*, const int64_t*, int64_t, hipStream_t);
-void mv_launch_sgd(float*, const float*, float*, float, int64_t, hipStream_t);
+void mv_launch_sgd(float*, const void*, void*, int, float, int64_t,
+                   hipStream_t);
 void mv_launch_sgd_f64(double*, const double*, double*, double, int64_t,
                        hipStream_t);
-void mv_launch_momentum(float*, float*, const float*, float*, float, int64_t,
-                        hipStream_t);
+void mv_launch_momentum(float*, float*, const void*, void*, int, float,
+                        int64_t, hipStream_t);
 void mv_launch_momentum_f64(double*, double*, const double*, double, int64_t,
                             hipStream_t);
-void mv_launch_adagrad(float*, float*, const float*, float*, float, float,
+void mv_launch_adagrad(float*, float*, const void*, void*, int, float, float,
                        float, int64_t, hipStream_t);
 void mv_launch_adagrad_f64(double*, double*, const double*, double, double,
                            double, int64_t, hipStream_t);
-void mv_launch_dcasgd(float*, float*, const float*, float*, float, float,
+void mv_launch_dcasgd(float*, float*, const void*, void*, int, float, float,
                       int64_t, hipStream_t);
-void mv_launch_dcasgda(float*, float*, float*, const float*, float*, float,
+void mv_launch_dcasgda(float*, float*, float*, const void*, void*, int, float,
                        float, float, float, int64_t, hipStream_t);
 // adam: (..., b1, b2, step = lr/(1-b1^t), rbc2 = 1/sqrt(1-b2^t),
 // decay = 1-lr*wd, eps, n), all scalars in double
-void mv_launch_adam(float*, float*, float*, const float*, float*, double,
+void mv_launch_adam(float*, float*, float*, const void*, void*, int, double,
                     double, double, double, double, double, int64_t,
                     hipStream_t);
 void mv_launch_adam_f64(double*, double*, double*, const double*, double,
                         double, double, double, double, double, int64_t,
                         hipStream_t);
-void mv_launch_row_gather(float*, const float*, const int64_t*, int64_t,
+// keyed kernels: `vals` (the gather's `out`) is void* followed by `wire`
+void mv_launch_row_gather(void*, int, const float*, const int64_t*, int64_t,
                           int64_t, hipStream_t);
-void mv_launch_row_scatter_add(float*, const float*, const int64_t*, float,
+void mv_launch_row_scatter_add(float*, const void*, int, const int64_t*, float,
                                int64_t, int64_t, int, hipStream_t);
 void mv_launch_w2v(float*, float*, float*, float*, const int64_t*, const int*,
                    const int64_t*, const float*, const int*, float, int64_t,
@@ -57,23 +60,24 @@ void mv_launch_lr_sigmoid_fwd(const float*, const int64_t*, const float*,
 void mv_launch_lr_sigmoid_scatter(float*, const int64_t*, const float*,
                                   const int*, const float*, float, int,
                                   float, int64_t, hipStream_t);
-void mv_launch_row_scatter_adagrad(float*, float*, const float*,
+void mv_launch_row_scatter_adagrad(float*, float*, const void*, int,
                                    const int64_t*, float, float, float,
                                    int64_t, int64_t, int, hipStream_t);
-// keyed stateful updaters: (shard, state..., vals, rows, perm-or-null,
+// keyed stateful updaters: (shard, state..., vals, wire, rows, perm-or-null,
 // scalars..., nrows, cols)
-void mv_launch_row_momentum(float*, float*, const float*, const int64_t*,
+void mv_launch_row_momentum(float*, float*, const void*, int, const int64_t*,
                             const int64_t*, float, int64_t, int64_t,
                             hipStream_t);
-void mv_launch_row_dcasgd(float*, float*, const float*, const int64_t*,
+void mv_launch_row_dcasgd(float*, float*, const void*, int, const int64_t*,
                           const int64_t*, float, float, int64_t, int64_t,
                           hipStream_t);
-void mv_launch_row_dcasgda(float*, float*, float*, const float*,
+void mv_launch_row_dcasgda(float*, float*, float*, const void*, int,
                            const int64_t*, const int64_t*, float, float,
                            float, float, int64_t, int64_t, hipStream_t);
-void mv_launch_row_adam(float*, float*, float*, const float*, const int64_t*,
-                        const int64_t*, double, double, double, double,
-                        double, double, int64_t, int64_t, hipStream_t);
+void mv_launch_row_adam(float*, float*, float*, const void*, int,
+                        const int64_t*, const int64_t*, double, double,
+                        double, double, double, double, int64_t, int64_t,
+                        hipStream_t);
 void mv_launch_lr_softmax_fwd(const float*, const int64_t*, const float*,
                               const int*, const float*, const float*,
                               float*, float*, int64_t, int64_t, hipStream_t);
@@ -132,18 +136,44 @@ int64_t check_same(std::initializer_list<Named> ts,
 float* f32(const torch::Tensor& t) { return t.data_ptr<float>(); }
 double* f64(const torch::Tensor& t) { return t.data_ptr<double>(); }
 
+// bf16 wire format: on an fp32 shard the delta (or vals) and the Get buffer
+// may hold bfloat16; the kernels widen and narrow in registers. The bits
+// match WIRE_DELTA / WIRE_OUT in kernels.hip.
+constexpr int kWireDelta = 1, kWireOut = 2;
+
+// Validates one such tensor (on the GPU, contiguous, n elements, of the
+// shard's dtype st or, where st is fp32, bf16) and returns `bit` if it
+// holds bf16, else 0. Without st the shard is fp32, worded as check_f32.
+int wire_bit(const torch::Tensor& t, const char* name, int64_t n, int bit,
+             c10::optional<torch::ScalarType> st = c10::nullopt) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.numel() == n, "size mismatch");
+  auto want = st.value_or(torch::kFloat32);
+  if (want == torch::kFloat32 && t.scalar_type() == torch::kBFloat16)
+    return bit;
+  if (st) {
+    TORCH_CHECK(t.scalar_type() == want, name, " dtype mismatch");
+  } else {
+    TORCH_CHECK(t.scalar_type() == want, name, " must be fp32 or bf16");
+  }
+  return 0;
+}
+
 void nt_copy(torch::Tensor dst, torch::Tensor src) {
-  int64_t n = check_same({{"dst", dst}, {"src", src}});
-  mv_launch_copy(f32(dst), f32(src), n, cur_stream());
+  int64_t n = check_same({{"src", src}});
+  int wire = wire_bit(dst, "dst", n, kWireOut);
+  mv_launch_copy(dst.data_ptr(), f32(src), wire, n, cur_stream());
 }
 
 void add_inplace(torch::Tensor data, torch::Tensor delta) {
   // dtype-dispatched K1 (reference instantiates int/float/double tables,
   // array_table.cpp:153-154; int updater is add-only, updater.cpp:40-43)
   auto st = data.scalar_type();
-  int64_t n = check_same({{"data", data}, {"delta", delta}}, st);
+  int64_t n = check_same({{"data", data}}, st);
+  int wire = wire_bit(delta, "delta", n, kWireDelta, st);
   if (st == torch::kFloat32)
-    mv_launch_add(f32(data), f32(delta), n, cur_stream());
+    mv_launch_add(f32(data), delta.data_ptr(), wire, n, cur_stream());
   else if (st == torch::kFloat64)
     mv_launch_add_f64(f64(data), f64(delta), n, cur_stream());
   else if (st == torch::kInt32)
@@ -159,11 +189,14 @@ void add_inplace(torch::Tensor data, torch::Tensor delta) {
 // data += sign * delta; `out`, when given, also receives the updated data
 void launch_sgd(const char* fn, const torch::Tensor& data,
                 const torch::Tensor& delta, const torch::Tensor* out,
-                double sign, int64_t n) {
+                double sign) {
   auto st = data.scalar_type();
+  int64_t n = check_same({{"data", data}}, st);
+  int wire = wire_bit(delta, "delta", n, kWireDelta, st);
+  if (out) wire |= wire_bit(*out, "out", n, kWireOut, st);
   if (st == torch::kFloat32)
-    mv_launch_sgd(f32(data), f32(delta), out ? f32(*out) : nullptr,
-                  (float)sign, n, cur_stream());
+    mv_launch_sgd(f32(data), delta.data_ptr(), out ? out->data_ptr() : nullptr,
+                  wire, (float)sign, n, cur_stream());
   else if (st == torch::kFloat64)
     mv_launch_sgd_f64(f64(data), f64(delta), out ? f64(*out) : nullptr, sign,
                       n, cur_stream());
@@ -172,25 +205,22 @@ void launch_sgd(const char* fn, const torch::Tensor& data,
 }
 
 void sgd_update(torch::Tensor data, torch::Tensor delta) {
-  int64_t n = check_same({{"data", data}, {"delta", delta}},
-                         data.scalar_type());
-  launch_sgd("sgd_update", data, delta, nullptr, -1.0, n);
+  launch_sgd("sgd_update", data, delta, nullptr, -1.0);
 }
 
 void sgd_copy_update(torch::Tensor data, torch::Tensor delta,
                      torch::Tensor out, double sign) {
-  int64_t n = check_same({{"data", data}, {"delta", delta}, {"out", out}},
-                         data.scalar_type());
-  launch_sgd("sgd_copy_update", data, delta, &out, sign, n);
+  launch_sgd("sgd_copy_update", data, delta, &out, sign);
 }
 
 void momentum_update(torch::Tensor data, torch::Tensor m, torch::Tensor delta,
                      double mu) {
   auto st = data.scalar_type();
-  int64_t n = check_same({{"data", data}, {"m", m}, {"delta", delta}}, st);
+  int64_t n = check_same({{"data", data}, {"m", m}}, st);
+  int wire = wire_bit(delta, "delta", n, kWireDelta, st);
   if (st == torch::kFloat32)
-    mv_launch_momentum(f32(data), f32(m), f32(delta), nullptr, (float)mu, n,
-                       cur_stream());
+    mv_launch_momentum(f32(data), f32(m), delta.data_ptr(), nullptr, wire,
+                       (float)mu, n, cur_stream());
   else if (st == torch::kFloat64)
     mv_launch_momentum_f64(f64(data), f64(m), f64(delta), mu, n,
                            cur_stream());
@@ -200,19 +230,21 @@ void momentum_update(torch::Tensor data, torch::Tensor m, torch::Tensor delta,
 
 void momentum_copy_update(torch::Tensor data, torch::Tensor m,
                           torch::Tensor delta, torch::Tensor out, double mu) {
-  int64_t n = check_same({{"data", data}, {"m", m}, {"delta", delta},
-                          {"out", out}});
-  mv_launch_momentum(f32(data), f32(m), f32(delta), f32(out), (float)mu, n,
-                     cur_stream());
+  int64_t n = check_same({{"data", data}, {"m", m}});
+  int wire = wire_bit(delta, "delta", n, kWireDelta) |
+             wire_bit(out, "out", n, kWireOut);
+  mv_launch_momentum(f32(data), f32(m), delta.data_ptr(), out.data_ptr(),
+                     wire, (float)mu, n, cur_stream());
 }
 
 void adagrad_update(torch::Tensor data, torch::Tensor gsq, torch::Tensor delta,
                     double lr, double rho, double eps) {
   auto st = data.scalar_type();
-  int64_t n = check_same({{"data", data}, {"gsq", gsq}, {"delta", delta}}, st);
+  int64_t n = check_same({{"data", data}, {"gsq", gsq}}, st);
+  int wire = wire_bit(delta, "delta", n, kWireDelta, st);
   if (st == torch::kFloat32)
-    mv_launch_adagrad(f32(data), f32(gsq), f32(delta), nullptr, (float)lr,
-                      (float)rho, (float)eps, n, cur_stream());
+    mv_launch_adagrad(f32(data), f32(gsq), delta.data_ptr(), nullptr, wire,
+                      (float)lr, (float)rho, (float)eps, n, cur_stream());
   else if (st == torch::kFloat64)
     mv_launch_adagrad_f64(f64(data), f64(gsq), f64(delta), lr, rho, eps, n,
                           cur_stream());
@@ -223,35 +255,38 @@ void adagrad_update(torch::Tensor data, torch::Tensor gsq, torch::Tensor delta,
 void adagrad_copy_update(torch::Tensor data, torch::Tensor gsq,
                          torch::Tensor delta, torch::Tensor out,
                          double lr, double rho, double eps) {
-  int64_t n = check_same({{"data", data}, {"gsq", gsq}, {"delta", delta},
-                          {"out", out}});
-  mv_launch_adagrad(f32(data), f32(gsq), f32(delta), f32(out), (float)lr,
-                    (float)rho, (float)eps, n, cur_stream());
+  int64_t n = check_same({{"data", data}, {"gsq", gsq}});
+  int wire = wire_bit(delta, "delta", n, kWireDelta) |
+             wire_bit(out, "out", n, kWireOut);
+  mv_launch_adagrad(f32(data), f32(gsq), delta.data_ptr(), out.data_ptr(),
+                    wire, (float)lr, (float)rho, (float)eps, n, cur_stream());
 }
 
 void dcasgd_update(torch::Tensor data, torch::Tensor bak, torch::Tensor delta,
                    double lr, double lambda) {
-  int64_t n = check_same({{"data", data}, {"bak", bak}, {"delta", delta}});
-  mv_launch_dcasgd(f32(data), f32(bak), f32(delta), nullptr, (float)lr,
-                   (float)lambda, n, cur_stream());
+  int64_t n = check_same({{"data", data}, {"bak", bak}});
+  int wire = wire_bit(delta, "delta", n, kWireDelta);
+  mv_launch_dcasgd(f32(data), f32(bak), delta.data_ptr(), nullptr, wire,
+                   (float)lr, (float)lambda, n, cur_stream());
 }
 
 void dcasgd_copy_update(torch::Tensor data, torch::Tensor bak,
                         torch::Tensor delta, torch::Tensor out,
                         double lr, double lambda) {
-  int64_t n = check_same({{"data", data}, {"bak", bak}, {"delta", delta},
-                          {"out", out}});
-  mv_launch_dcasgd(f32(data), f32(bak), f32(delta), f32(out), (float)lr,
-                   (float)lambda, n, cur_stream());
+  int64_t n = check_same({{"data", data}, {"bak", bak}});
+  int wire = wire_bit(delta, "delta", n, kWireDelta) |
+             wire_bit(out, "out", n, kWireOut);
+  mv_launch_dcasgd(f32(data), f32(bak), delta.data_ptr(), out.data_ptr(),
+                   wire, (float)lr, (float)lambda, n, cur_stream());
 }
 
 void dcasgda_update(torch::Tensor data, torch::Tensor bak, torch::Tensor msq,
                     torch::Tensor delta, double lr, double lambda, double rho,
                     double eps) {
-  int64_t n = check_same({{"data", data}, {"bak", bak}, {"msq", msq},
-                          {"delta", delta}});
-  mv_launch_dcasgda(f32(data), f32(bak), f32(msq), f32(delta), nullptr,
-                    (float)lr, (float)lambda, (float)rho, (float)eps, n,
+  int64_t n = check_same({{"data", data}, {"bak", bak}, {"msq", msq}});
+  int wire = wire_bit(delta, "delta", n, kWireDelta);
+  mv_launch_dcasgda(f32(data), f32(bak), f32(msq), delta.data_ptr(), nullptr,
+                    wire, (float)lr, (float)lambda, (float)rho, (float)eps, n,
                     cur_stream());
 }
 
@@ -259,11 +294,12 @@ void dcasgda_copy_update(torch::Tensor data, torch::Tensor bak,
                          torch::Tensor msq, torch::Tensor delta,
                          torch::Tensor out, double lr, double lambda,
                          double rho, double eps) {
-  int64_t n = check_same({{"data", data}, {"bak", bak}, {"msq", msq},
-                          {"delta", delta}, {"out", out}});
-  mv_launch_dcasgda(f32(data), f32(bak), f32(msq), f32(delta), f32(out),
-                    (float)lr, (float)lambda, (float)rho, (float)eps, n,
-                    cur_stream());
+  int64_t n = check_same({{"data", data}, {"bak", bak}, {"msq", msq}});
+  int wire = wire_bit(delta, "delta", n, kWireDelta) |
+             wire_bit(out, "out", n, kWireOut);
+  mv_launch_dcasgda(f32(data), f32(bak), f32(msq), delta.data_ptr(),
+                    out.data_ptr(), wire, (float)lr, (float)lambda,
+                    (float)rho, (float)eps, n, cur_stream());
 }
 
 // step = lr / (1 - b1^t), rbc2 = 1 / sqrt(1 - b2^t), decay = 1 - lr*wd:
@@ -272,11 +308,11 @@ void adam_update(torch::Tensor data, torch::Tensor m, torch::Tensor v,
                  torch::Tensor delta, double b1, double b2, double step,
                  double rbc2, double decay, double eps) {
   auto st = data.scalar_type();
-  int64_t n = check_same({{"data", data}, {"m", m}, {"v", v},
-                          {"delta", delta}}, st);
+  int64_t n = check_same({{"data", data}, {"m", m}, {"v", v}}, st);
+  int wire = wire_bit(delta, "delta", n, kWireDelta, st);
   if (st == torch::kFloat32)
-    mv_launch_adam(f32(data), f32(m), f32(v), f32(delta), nullptr, b1, b2,
-                   step, rbc2, decay, eps, n, cur_stream());
+    mv_launch_adam(f32(data), f32(m), f32(v), delta.data_ptr(), nullptr, wire,
+                   b1, b2, step, rbc2, decay, eps, n, cur_stream());
   else if (st == torch::kFloat64)
     mv_launch_adam_f64(f64(data), f64(m), f64(v), f64(delta), b1, b2, step,
                        rbc2, decay, eps, n, cur_stream());
@@ -288,44 +324,47 @@ void adam_copy_update(torch::Tensor data, torch::Tensor m, torch::Tensor v,
                       torch::Tensor delta, torch::Tensor out, double b1,
                       double b2, double step, double rbc2, double decay,
                       double eps) {
-  int64_t n = check_same({{"data", data}, {"m", m}, {"v", v},
-                          {"delta", delta}, {"out", out}});
-  mv_launch_adam(f32(data), f32(m), f32(v), f32(delta), f32(out), b1, b2,
-                 step, rbc2, decay, eps, n, cur_stream());
+  int64_t n = check_same({{"data", data}, {"m", m}, {"v", v}});
+  int wire = wire_bit(delta, "delta", n, kWireDelta) |
+             wire_bit(out, "out", n, kWireOut);
+  mv_launch_adam(f32(data), f32(m), f32(v), delta.data_ptr(), out.data_ptr(),
+                 wire, b1, b2, step, rbc2, decay, eps, n, cur_stream());
 }
 
-torch::Tensor row_gather(torch::Tensor shard, torch::Tensor rows) {
+void row_gather_out(torch::Tensor out, torch::Tensor shard, torch::Tensor rows) {
   check_f32(shard, "shard");
   TORCH_CHECK(shard.dim() == 2, "shard must be 2-D");
   TORCH_CHECK(rows.scalar_type() == torch::kInt64 && rows.is_cuda() &&
               rows.is_contiguous(), "rows must be contiguous int64 on GPU");
-  auto out = torch::empty({rows.numel(), shard.size(1)}, shard.options());
-  mv_launch_row_gather(out.data_ptr<float>(), shard.data_ptr<float>(),
+  TORCH_CHECK(out.numel() == rows.numel() * shard.size(1), "out size mismatch");
+  int wire = wire_bit(out, "out", out.numel(), kWireOut);
+  mv_launch_row_gather(out.data_ptr(), wire, shard.data_ptr<float>(),
                        rows.data_ptr<int64_t>(), rows.numel(), shard.size(1),
                        cur_stream());
-  return out;
 }
 
-void row_gather_out(torch::Tensor out, torch::Tensor shard, torch::Tensor rows) {
-  check_f32(shard, "shard"); check_f32(out, "out");
+// dtype: the result's, fp32 (the default) or bf16
+torch::Tensor row_gather(torch::Tensor shard, torch::Tensor rows,
+                         c10::optional<torch::ScalarType> dtype) {
+  check_f32(shard, "shard");
   TORCH_CHECK(shard.dim() == 2, "shard must be 2-D");
-  TORCH_CHECK(rows.scalar_type() == torch::kInt64 && rows.is_cuda() &&
-              rows.is_contiguous(), "rows must be contiguous int64 on GPU");
-  TORCH_CHECK(out.numel() == rows.numel() * shard.size(1), "out size mismatch");
-  mv_launch_row_gather(out.data_ptr<float>(), shard.data_ptr<float>(),
-                       rows.data_ptr<int64_t>(), rows.numel(), shard.size(1),
-                       cur_stream());
+  auto out = torch::empty({rows.numel(), shard.size(1)},
+                          shard.options().dtype(
+                              dtype.value_or(torch::kFloat32)));
+  row_gather_out(out, shard, rows);
+  return out;
 }
 
 void row_scatter_add(torch::Tensor shard, torch::Tensor rows,
                      torch::Tensor vals, double sign,
                      bool assume_unique = false) {
-  check_f32(shard, "shard"); check_f32(vals, "vals");
+  check_f32(shard, "shard");
   TORCH_CHECK(shard.dim() == 2, "shard must be 2-D");
   TORCH_CHECK(rows.scalar_type() == torch::kInt64 && rows.is_cuda() &&
               rows.is_contiguous(), "rows must be contiguous int64 on GPU");
   TORCH_CHECK(vals.numel() == rows.numel() * shard.size(1), "vals size mismatch");
-  mv_launch_row_scatter_add(shard.data_ptr<float>(), vals.data_ptr<float>(),
+  int wire = wire_bit(vals, "vals", vals.numel(), kWireDelta);
+  mv_launch_row_scatter_add(shard.data_ptr<float>(), vals.data_ptr(), wire,
                             rows.data_ptr<int64_t>(), (float)sign,
                             rows.numel(), shard.size(1),
                             assume_unique ? 1 : 0, cur_stream());
@@ -335,26 +374,29 @@ void row_scatter_adagrad(torch::Tensor shard, torch::Tensor gsq,
                          torch::Tensor rows, torch::Tensor vals,
                          double lr, double rho, double eps,
                          bool assume_unique = false) {
-  check_f32(shard, "shard"); check_f32(gsq, "gsq"); check_f32(vals, "vals");
+  check_f32(shard, "shard"); check_f32(gsq, "gsq");
   TORCH_CHECK(shard.dim() == 2, "shard must be 2-D");
   TORCH_CHECK(gsq.sizes() == shard.sizes(), "gsq shape mismatch");
   TORCH_CHECK(rows.scalar_type() == torch::kInt64 && rows.is_cuda() &&
               rows.is_contiguous(), "rows must be contiguous int64 on GPU");
   TORCH_CHECK(vals.numel() == rows.numel() * shard.size(1), "vals mismatch");
+  int wire = wire_bit(vals, "vals", vals.numel(), kWireDelta);
   mv_launch_row_scatter_adagrad(
-      shard.data_ptr<float>(), gsq.data_ptr<float>(), vals.data_ptr<float>(),
+      shard.data_ptr<float>(), gsq.data_ptr<float>(), vals.data_ptr(), wire,
       rows.data_ptr<int64_t>(), (float)lr, (float)rho, (float)eps,
       rows.numel(), shard.size(1), assume_unique ? 1 : 0, cur_stream());
 }
 
 // Validation shared by the keyed stateful updaters; returns perm's data
-// pointer, or null for the identity.
+// pointer, or null for the identity, and in `wire` whether vals holds bf16.
 const int64_t* check_row_update(const torch::Tensor& shard,
                                 std::initializer_list<Named> state,
                                 const torch::Tensor& rows,
                                 const torch::Tensor& vals,
-                                const c10::optional<torch::Tensor>& perm) {
-  check_f32(shard, "shard"); check_f32(vals, "vals");
+                                const c10::optional<torch::Tensor>& perm,
+                                int* wire) {
+  check_f32(shard, "shard");
+  *wire = wire_bit(vals, "vals", vals.numel(), kWireDelta);
   TORCH_CHECK(shard.dim() == 2, "shard must be 2-D");
   for (const auto& t : state) {
     check_f32(t.second, t.first);
@@ -374,8 +416,10 @@ const int64_t* check_row_update(const torch::Tensor& shard,
 void row_momentum_update(torch::Tensor shard, torch::Tensor m,
                          torch::Tensor rows, torch::Tensor vals, double mu,
                          c10::optional<torch::Tensor> perm) {
-  const int64_t* pp = check_row_update(shard, {{"m", m}}, rows, vals, perm);
-  mv_launch_row_momentum(f32(shard), f32(m), f32(vals),
+  int wire;
+  const int64_t* pp = check_row_update(shard, {{"m", m}}, rows, vals, perm,
+                                       &wire);
+  mv_launch_row_momentum(f32(shard), f32(m), vals.data_ptr(), wire,
                          rows.data_ptr<int64_t>(), pp, (float)mu,
                          rows.numel(), shard.size(1), cur_stream());
 }
@@ -383,9 +427,10 @@ void row_momentum_update(torch::Tensor shard, torch::Tensor m,
 void row_dcasgd_update(torch::Tensor shard, torch::Tensor bak,
                        torch::Tensor rows, torch::Tensor vals, double lr,
                        double lambda, c10::optional<torch::Tensor> perm) {
+  int wire;
   const int64_t* pp = check_row_update(shard, {{"bak", bak}}, rows, vals,
-                                       perm);
-  mv_launch_row_dcasgd(f32(shard), f32(bak), f32(vals),
+                                       perm, &wire);
+  mv_launch_row_dcasgd(f32(shard), f32(bak), vals.data_ptr(), wire,
                        rows.data_ptr<int64_t>(), pp, (float)lr,
                        (float)lambda, rows.numel(), shard.size(1),
                        cur_stream());
@@ -396,9 +441,10 @@ void row_dcasgda_update(torch::Tensor shard, torch::Tensor bak,
                         torch::Tensor vals, double lr, double lambda,
                         double rho, double eps,
                         c10::optional<torch::Tensor> perm) {
+  int wire;
   const int64_t* pp = check_row_update(shard, {{"bak", bak}, {"msq", msq}},
-                                       rows, vals, perm);
-  mv_launch_row_dcasgda(f32(shard), f32(bak), f32(msq), f32(vals),
+                                       rows, vals, perm, &wire);
+  mv_launch_row_dcasgda(f32(shard), f32(bak), f32(msq), vals.data_ptr(), wire,
                         rows.data_ptr<int64_t>(), pp, (float)lr,
                         (float)lambda, (float)rho, (float)eps, rows.numel(),
                         shard.size(1), cur_stream());
@@ -408,9 +454,10 @@ void row_adam_update(torch::Tensor shard, torch::Tensor m, torch::Tensor v,
                      torch::Tensor rows, torch::Tensor vals, double b1,
                      double b2, double step, double rbc2, double decay,
                      double eps, c10::optional<torch::Tensor> perm) {
+  int wire;
   const int64_t* pp = check_row_update(shard, {{"m", m}, {"v", v}}, rows,
-                                       vals, perm);
-  mv_launch_row_adam(f32(shard), f32(m), f32(v), f32(vals),
+                                       vals, perm, &wire);
+  mv_launch_row_adam(f32(shard), f32(m), f32(v), vals.data_ptr(), wire,
                      rows.data_ptr<int64_t>(), pp, b1, b2, step, rbc2, decay,
                      eps, rows.numel(), shard.size(1), cur_stream());
 }
@@ -674,8 +721,10 @@ void lr_ftrl_scatter(torch::Tensor zn, torch::Tensor keys,
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  // fp32 shards also take a bf16 delta / vals / out (the bf16 wire format)
   m.def("add_inplace", &add_inplace, "K1: data += delta (fp32, fused)");
-  m.def("nt_copy", &nt_copy, "K7: non-temporal streaming copy");
+  m.def("nt_copy", &nt_copy,
+        "K7: non-temporal streaming copy (a bf16 dst narrows)");
   m.def("sgd_update", &sgd_update, "K2: data -= delta");
   m.def("momentum_update", &momentum_update, "K3: fused momentum update");
   m.def("adagrad_update", &adagrad_update, "K4: fused adagrad update");
@@ -704,7 +753,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("data"), py::arg("m"), py::arg("v"), py::arg("delta"),
         py::arg("out"), py::arg("b1"), py::arg("b2"), py::arg("step"),
         py::arg("rbc2"), py::arg("decay"), py::arg("eps"));
-  m.def("row_gather", &row_gather, "K6: out[i] = shard[rows[i]]");
+  m.def("row_gather", &row_gather,
+        "K6: out[i] = shard[rows[i]]; dtype=torch.bfloat16 narrows",
+        py::arg("shard"), py::arg("rows"), py::arg("dtype") = py::none());
   m.def("row_gather_out", &row_gather_out, "K6 (preallocated out)");
   m.def("row_scatter_add", &row_scatter_add,
         "K5: shard[rows[i]] += sign*vals[i] (atomic; assume_unique=True "

@@ -86,6 +86,84 @@ static __device__ __forceinline__ void st(T* p, int64_t i, V v) {
   ntstore((V*)p + i, v);
 }
 
+// bf16 wire format: the delta / vals a kernel reads and the Get buffer it
+// writes may hold bfloat16 while the shard and all state stay fp32. bf16 is
+// storage only: the ld/st overloads below widen on load and narrow on
+// store, so every formula keeps its one fp32 body. A V of 4 (2) floats
+// moves as one 8-byte (4-byte) access; those need that alignment, which the
+// launchers check.
+struct bf16 { uint16_t bits; };
+typedef uint16_t v4h __attribute__((ext_vector_type(4)));
+typedef uint16_t v2h __attribute__((ext_vector_type(2)));
+
+// exact: bf16 is the top half of the fp32 with the same value
+static __device__ __forceinline__ float widen(uint16_t h) {
+  return __builtin_bit_cast(float, (uint32_t)h << 16);
+}
+// round to nearest even with gfx950's packed convert (v_cvt_pk_bf16_f32).
+// Checked on the device over all 2^32 inputs against the integer form
+// (u + 0x7FFF + ((u >> 16) & 1)) >> 16, which is torch's .to(torch.bfloat16):
+// equal bits for every finite value and +-inf (denormals round like any
+// other value, a large finite value carries into inf), and a NaN stays a NaN
+// (tools/probe_bf16_cvt.hip, profiles/bf16_wire.md)
+static __device__ __forceinline__ uint16_t narrow(float f) {
+  return __builtin_bit_cast(uint16_t, (__bf16)f);
+}
+
+template <class V>
+static __device__ __forceinline__ V ld(const bf16* p, int64_t i) {
+  if constexpr (std::is_same<V, v4f>::value) {
+    v4h h = __builtin_nontemporal_load((const v4h*)p + i);
+    v4f v;
+    v.x = widen(h.x); v.y = widen(h.y); v.z = widen(h.z); v.w = widen(h.w);
+    return v;
+  } else {
+    static_assert(std::is_same<V, float>::value, "bf16 widens to fp32");
+    return widen(p[i].bits);
+  }
+}
+// V = v4f (non-temporal, the streaming kernels), float4 / float2 (plain, the
+// row gather) or float
+template <class V>
+static __device__ __forceinline__ void st(bf16* p, int64_t i, V v) {
+  if constexpr (sizeof(V) == 16) {
+    v4h h;
+    h.x = narrow(v.x); h.y = narrow(v.y); h.z = narrow(v.z); h.w = narrow(v.w);
+    if constexpr (std::is_same<V, v4f>::value)
+      __builtin_nontemporal_store(h, (v4h*)p + i);
+    else
+      *((v4h*)p + i) = h;
+  } else if constexpr (sizeof(V) == 8) {
+    v2h h;
+    h.x = narrow(v.x); h.y = narrow(v.y);
+    *((v2h*)p + i) = h;
+  } else {
+    p[i].bits = narrow(v);
+  }
+}
+
+// which pointers of a launch hold bf16 (the `wire` argument of the
+// launchers below): the delta or vals, the Get buffer
+#define WIRE_DELTA 1
+#define WIRE_OUT 2
+#define ELEM_OF(p) std::remove_cv_t<std::remove_pointer_t<decltype(p)>>
+
+// f(delta, out) with each pointer cast to what `wire` says it holds
+template <class F>
+static void with_wire(int wire, const void* delta, void* out, F f) {
+  switch (wire & (WIRE_DELTA | WIRE_OUT)) {
+    case 0: f((const float*)delta, (float*)out); break;
+    case WIRE_DELTA: f((const bf16*)delta, (float*)out); break;
+    case WIRE_OUT: f((const float*)delta, (bf16*)out); break;
+    default: f((const bf16*)delta, (bf16*)out);
+  }
+}
+
+// fp32 buffers are 16-byte aligned torch allocations; a bf16 one can be a
+// view such as x[1:] or a slice of a staged blob, 2 bytes off
+static inline bool vec_ok(const float*) { return true; }
+static inline bool vec_ok(const bf16* p) { return ((uintptr_t)p & 7) == 0; }
+
 static inline int grid_for_cap(int64_t work_items, int cap,
                                int block = BLOCK) {
   int64_t blocks = (work_items + block - 1) / block;
@@ -105,6 +183,7 @@ static inline int grid_for(int64_t work_items) {
 // 16B-aligned torch allocs); double (every updater the reference
 // instantiates, array_table.cpp:153-154) and int32/int64 (add-only,
 // updater.cpp:40-43) run the same ops with V = T, plain scalar access.
+// D is the delta's element type: T, or bf16 on an fp32 shard (widened by ld).
 // Every step issues all its loads before its first store: struct members
 // carry no __restrict__, so a load written after a store would wait for it.
 // The momentum, DC-ASGD and Adam ops keep their formula in
@@ -113,10 +192,10 @@ static inline int grid_for(int64_t work_items) {
 // instead.
 // ---------------------------------------------------------------------------
 
-template <class T>
+template <class T, class D = T>
 struct AddOp {
   using elem = T;
-  T* data; const T* delta;
+  T* data; const D* delta;
   template <class V> __device__ __forceinline__ V step(int64_t i) const {
     V v = ld<V>(data, i) + ld<V>(delta, i);
     st(data, i, v);
@@ -126,10 +205,10 @@ struct AddOp {
 
 // sign = -1 is sgd; the fused Add+Get passes +1 for the default (add)
 // updater.
-template <class T>
+template <class T, class D = T>
 struct SgdOp {
   using elem = T;
-  T* data; const T* delta; T sign;
+  T* data; const D* delta; T sign;
   template <class V> __device__ __forceinline__ V step(int64_t i) const {
     V v = ld<V>(data, i) + sign * ld<V>(delta, i);
     st(data, i, v);
@@ -137,10 +216,10 @@ struct SgdOp {
   }
 };
 
-template <class T>
+template <class T, class D = T>
 struct MomentumOp {
   using elem = T;
-  T* data; T* m; const T* delta; T mu;
+  T* data; T* m; const D* delta; T mu;
   template <class V> __device__ __forceinline__ V step_at(int64_t i,
                                                           V g) const {
     V d = ld<V>(data, i);
@@ -158,10 +237,10 @@ struct MomentumOp {
   }
 };
 
-template <class T>
+template <class T, class D = T>
 struct AdagradOp {
   using elem = T;
-  T* data; T* gsq; const T* delta; T inv_lr, rho, eps;
+  T* data; T* gsq; const D* delta; T inv_lr, rho, eps;
   template <class V> __device__ __forceinline__ V step(int64_t i) const {
     V d = ld<V>(data, i), G = ld<V>(gsq, i);
     V g = ld<V>(delta, i) * inv_lr;
@@ -186,9 +265,10 @@ struct AdagradOp {
 //   bak   = w            (per-worker backup, updated after the step)
 // Adaptive variant keeps a mean-square m = rho*m + (1-rho)*g*g and uses
 // lambda / sqrt(m + eps) as the compensation coefficient.
+template <class D = float>
 struct DcasgdOp {
   using elem = float;
-  float* data; float* bak; const float* delta; float lr, lambda;
+  float* data; float* bak; const D* delta; float lr, lambda;
   template <class V> __device__ __forceinline__ V step_at(int64_t i,
                                                           V g) const {
     V w = ld<V>(data, i), b = ld<V>(bak, i);
@@ -202,9 +282,10 @@ struct DcasgdOp {
   }
 };
 
+template <class D = float>
 struct DcasgdaOp {
   using elem = float;
-  float* data; float* bak; float* msq; const float* delta;
+  float* data; float* bak; float* msq; const D* delta;
   float lr, lambda, rho, eps;
   template <class V> __device__ __forceinline__ V step_at(int64_t i,
                                                           V g) const {
@@ -236,10 +317,10 @@ struct DcasgdaOp {
 // the rsq helper). Every multiply-add that could contract is an explicit
 // fma, as in MomentumOp: the v4f body, the scalar tail and k_row_update
 // must round alike.
-template <class T>
+template <class T, class D = T>
 struct AdamOp {
   using elem = T;
-  T* data; T* m; T* v; const T* delta;
+  T* data; T* m; T* v; const D* delta;
   T b1, omb1, b2, omb2, alpha, rbc2, decay, eps;
   template <class V> __device__ __forceinline__ V step_at(int64_t i,
                                                           V g) const {
@@ -261,18 +342,20 @@ struct AdamOp {
 
 // Adam's scalars arrive in double (the host's bias corrections and decay
 // factor) and are rounded to the table's type once, here.
-template <class T>
-static AdamOp<T> adam_op(T* data, T* m, T* v, const T* delta, double b1,
-                         double b2, double step, double rbc2, double decay,
-                         double eps) {
-  return AdamOp<T>{data, m, v, delta, (T)b1, (T)(1.0 - b1), (T)b2,
-                   (T)(1.0 - b2), (T)step, (T)rbc2, (T)decay, (T)eps};
+template <class T, class D>
+static AdamOp<T, D> adam_op(T* data, T* m, T* v, const D* delta, double b1,
+                            double b2, double step, double rbc2, double decay,
+                            double eps) {
+  return AdamOp<T, D>{data, m, v, delta, (T)b1, (T)(1.0 - b1), (T)b2,
+                      (T)(1.0 - b2), (T)step, (T)rbc2, (T)decay, (T)eps};
 }
 
-// K7 Access / shard copy-out: non-temporal streaming copy.
+// K7 Access / shard copy-out: non-temporal streaming copy; O = bf16 narrows
+// the shard into a bf16 Get buffer.
+template <class O = float>
 struct CopyOp {
   using elem = float;
-  float* dst; const float* src;
+  O* dst; const float* src;
   template <class V> __device__ __forceinline__ V step(int64_t i) const {
     V v = ld<V>(src, i);
     st(dst, i, v);
@@ -287,123 +370,162 @@ struct CopyOp {
 // saves that re-read — 2.0 GB instead of 2.5 GB per Add+Get step on the
 // 1e6x128 headline config (observable semantics identical: shard updated
 // AND out filled with the updated values).
-template <class Op, class V, bool COPY>
-__global__ void k_elem(Op op, V* __restrict__ out, int64_t start, int64_t n) {
+// `out` is the Get buffer, an array of O (the shard's type, or bf16) that
+// st views as V like the op's own arrays.
+template <class Op, class V, bool COPY, class O>
+__global__ void k_elem(Op op, O* __restrict__ out, int64_t start, int64_t n) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = start + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i < n; i += stride) {
     V v = op.template step<V>(i);
-    if (COPY) ntstore(&out[i], v);
+    if (COPY) st(out, i, v);
   }
 }
 
 // fp32: float4 body over n/4 vectors with the given grid cap and block,
-// then one wave over the n%4 scalar tail. Other types: scalar grid-stride.
-template <bool COPY, class Op>
-static void launch_elem(const Op& op, typename Op::elem* out, int64_t n,
-                        int cap, int block, hipStream_t s) {
+// then one wave over the n%4 scalar tail. Other types, and fp32 with
+// vec = false (a bf16 pointer that is not 8-byte aligned): scalar
+// grid-stride.
+template <bool COPY, class Op, class O>
+static void launch_elem(const Op& op, O* out, int64_t n, int cap, int block,
+                        hipStream_t s, bool vec = true) {
   using T = typename Op::elem;
   if constexpr (std::is_same<T, float>::value) {
-    int64_t n4 = n / 4;
-    if (n4) k_elem<Op, v4f, COPY><<<grid_for_cap(n4, cap, block), block, 0,
-                                    s>>>(op, (v4f*)out, 0, n4);
-    if (n > n4 * 4) k_elem<Op, float, COPY><<<1, 64, 0, s>>>(op, out, n4 * 4,
-                                                             n);
-  } else if (n > 0) {
+    if (vec) {
+      int64_t n4 = n / 4;
+      if (n4) k_elem<Op, v4f, COPY><<<grid_for_cap(n4, cap, block), block, 0,
+                                      s>>>(op, out, 0, n4);
+      if (n > n4 * 4) k_elem<Op, float, COPY><<<1, 64, 0, s>>>(op, out,
+                                                               n4 * 4, n);
+      return;
+    }
+  }
+  if (n > 0)
     k_elem<Op, T, COPY><<<grid_for_cap(n, cap, block), block, 0, s>>>(
         op, out, 0, n);
-  }
 }
 
 // fp32 updater launch: a non-null `out` selects the fused Add+Get form
 // with its fat-block geometry (COPY_BLOCK x COPY_GRID, see the sweep note
-// at the COPY_BLOCK define); otherwise BLOCK threads x `cap` blocks.
-template <class Op>
-static void launch_update(const Op& op, float* out, int64_t n, int cap,
+// at the COPY_BLOCK define); otherwise BLOCK threads x `cap` blocks. The
+// bf16 forms keep the geometry of their fp32 siblings.
+template <class Op, class O>
+static void launch_update(const Op& op, O* out, int64_t n, int cap,
                           hipStream_t s) {
-  if (out) launch_elem<true>(op, out, n, COPY_GRID, COPY_BLOCK, s);
-  else launch_elem<false>(op, nullptr, n, cap, BLOCK, s);
+  bool vec = vec_ok(op.delta) && vec_ok(out);
+  if (out) launch_elem<true>(op, out, n, COPY_GRID, COPY_BLOCK, s, vec);
+  else launch_elem<false>(op, (float*)nullptr, n, cap, BLOCK, s, vec);
 }
 
 extern "C" {
 
-void mv_launch_copy(float* dst, const float* src, int64_t n, hipStream_t s) {
-  launch_elem<false>(CopyOp{dst, src}, nullptr, n, ELEM_GRID, BLOCK, s);
+// The fp32 launchers take the delta and the Get buffer as void* plus the
+// WIRE_* bits that say which of the two holds bf16.
+void mv_launch_copy(void* dst, const float* src, int wire, int64_t n,
+                    hipStream_t s) {
+  with_wire(wire, nullptr, dst, [&](auto*, auto* o) {
+    launch_elem<false>(CopyOp<ELEM_OF(o)>{o, src}, (float*)nullptr, n,
+                       ELEM_GRID, BLOCK, s, vec_ok(o));
+  });
 }
 
-void mv_launch_add(float* data, const float* delta, int64_t n, hipStream_t s) {
-  launch_elem<false>(AddOp<float>{data, delta}, nullptr, n, UPD_GRID, BLOCK, s);
+void mv_launch_add(float* data, const void* delta, int wire, int64_t n,
+                   hipStream_t s) {
+  with_wire(wire, delta, nullptr, [&](auto* d, auto*) {
+    launch_elem<false>(AddOp<float, ELEM_OF(d)>{data, d}, (float*)nullptr, n,
+                       UPD_GRID, BLOCK, s, vec_ok(d));
+  });
 }
 void mv_launch_add_f64(double* d, const double* x, int64_t n, hipStream_t s) {
-  launch_elem<false>(AddOp<double>{d, x}, nullptr, n, ELEM_GRID, BLOCK, s);
+  launch_elem<false>(AddOp<double>{d, x}, (double*)nullptr, n, ELEM_GRID,
+                     BLOCK, s);
 }
 void mv_launch_add_i32(int32_t* d, const int32_t* x, int64_t n, hipStream_t s) {
-  launch_elem<false>(AddOp<int32_t>{d, x}, nullptr, n, ELEM_GRID, BLOCK, s);
+  launch_elem<false>(AddOp<int32_t>{d, x}, (int32_t*)nullptr, n, ELEM_GRID,
+                     BLOCK, s);
 }
 void mv_launch_add_i64(int64_t* d, const int64_t* x, int64_t n, hipStream_t s) {
-  launch_elem<false>(AddOp<int64_t>{d, x}, nullptr, n, ELEM_GRID, BLOCK, s);
+  launch_elem<false>(AddOp<int64_t>{d, x}, (int64_t*)nullptr, n, ELEM_GRID,
+                     BLOCK, s);
 }
 
-void mv_launch_sgd(float* data, const float* delta, float* out, float sign,
-                   int64_t n, hipStream_t s) {
-  launch_update(SgdOp<float>{data, delta, sign}, out, n, UPD_GRID, s);
+void mv_launch_sgd(float* data, const void* delta, void* out, int wire,
+                   float sign, int64_t n, hipStream_t s) {
+  with_wire(wire, delta, out, [&](auto* d, auto* o) {
+    launch_update(SgdOp<float, ELEM_OF(d)>{data, d, sign}, o, n, UPD_GRID, s);
+  });
 }
 void mv_launch_sgd_f64(double* d, const double* x, double* out, double sign,
                        int64_t n, hipStream_t s) {
   SgdOp<double> op{d, x, sign};
   if (out) launch_elem<true>(op, out, n, STATE_GRID, BLOCK, s);
-  else launch_elem<false>(op, nullptr, n, ELEM_GRID, BLOCK, s);
+  else launch_elem<false>(op, out, n, ELEM_GRID, BLOCK, s);
 }
 
-void mv_launch_momentum(float* data, float* m, const float* delta, float* out,
-                        float mu, int64_t n, hipStream_t s) {
-  launch_update(MomentumOp<float>{data, m, delta, mu}, out, n, STATE_GRID, s);
+void mv_launch_momentum(float* data, float* m, const void* delta, void* out,
+                        int wire, float mu, int64_t n, hipStream_t s) {
+  with_wire(wire, delta, out, [&](auto* d, auto* o) {
+    launch_update(MomentumOp<float, ELEM_OF(d)>{data, m, d, mu}, o, n,
+                  STATE_GRID, s);
+  });
 }
 void mv_launch_momentum_f64(double* d, double* m, const double* x, double mu,
                             int64_t n, hipStream_t s) {
-  launch_elem<false>(MomentumOp<double>{d, m, x, mu}, nullptr, n, STATE_GRID,
-                     BLOCK, s);
+  launch_elem<false>(MomentumOp<double>{d, m, x, mu}, (double*)nullptr, n,
+                     STATE_GRID, BLOCK, s);
 }
 
-void mv_launch_adagrad(float* data, float* gsq, const float* delta, float* out,
-                       float lr, float rho, float eps, int64_t n,
+void mv_launch_adagrad(float* data, float* gsq, const void* delta, void* out,
+                       int wire, float lr, float rho, float eps, int64_t n,
                        hipStream_t s) {
-  launch_update(AdagradOp<float>{data, gsq, delta, 1.0f / lr, rho, eps}, out,
-                n, STATE_GRID, s);
+  with_wire(wire, delta, out, [&](auto* d, auto* o) {
+    launch_update(AdagradOp<float, ELEM_OF(d)>{data, gsq, d, 1.0f / lr, rho,
+                                               eps},
+                  o, n, STATE_GRID, s);
+  });
 }
 void mv_launch_adagrad_f64(double* d, double* g, const double* x, double lr,
                            double rho, double eps, int64_t n, hipStream_t s) {
-  launch_elem<false>(AdagradOp<double>{d, g, x, 1.0 / lr, rho, eps}, nullptr,
-                     n, STATE_GRID, BLOCK, s);
+  launch_elem<false>(AdagradOp<double>{d, g, x, 1.0 / lr, rho, eps},
+                     (double*)nullptr, n, STATE_GRID, BLOCK, s);
 }
 
-void mv_launch_dcasgd(float* data, float* bak, const float* delta, float* out,
-                      float lr, float lambda, int64_t n, hipStream_t s) {
-  launch_update(DcasgdOp{data, bak, delta, lr, lambda}, out, n, STATE_GRID, s);
+void mv_launch_dcasgd(float* data, float* bak, const void* delta, void* out,
+                      int wire, float lr, float lambda, int64_t n,
+                      hipStream_t s) {
+  with_wire(wire, delta, out, [&](auto* d, auto* o) {
+    launch_update(DcasgdOp<ELEM_OF(d)>{data, bak, d, lr, lambda}, o, n,
+                  STATE_GRID, s);
+  });
 }
 
-void mv_launch_dcasgda(float* data, float* bak, float* msq, const float* delta,
-                       float* out, float lr, float lambda, float rho,
+void mv_launch_dcasgda(float* data, float* bak, float* msq, const void* delta,
+                       void* out, int wire, float lr, float lambda, float rho,
                        float eps, int64_t n, hipStream_t s) {
-  launch_update(DcasgdaOp{data, bak, msq, delta, lr, lambda, rho, eps}, out,
-                n, STATE_GRID, s);
+  with_wire(wire, delta, out, [&](auto* d, auto* o) {
+    launch_update(DcasgdaOp<ELEM_OF(d)>{data, bak, msq, d, lr, lambda, rho,
+                                        eps},
+                  o, n, STATE_GRID, s);
+  });
 }
 
 // Geometry is the other stateful updaters' STATE_GRID (COPY_BLOCK x
 // COPY_GRID with `out`): no grid sweep has been run for a 4-read/3-write
 // stream.
-void mv_launch_adam(float* data, float* m, float* v, const float* delta,
-                    float* out, double b1, double b2, double step,
+void mv_launch_adam(float* data, float* m, float* v, const void* delta,
+                    void* out, int wire, double b1, double b2, double step,
                     double rbc2, double decay, double eps, int64_t n,
                     hipStream_t s) {
-  launch_update(adam_op(data, m, v, delta, b1, b2, step, rbc2, decay, eps),
-                out, n, STATE_GRID, s);
+  with_wire(wire, delta, out, [&](auto* d, auto* o) {
+    launch_update(adam_op(data, m, v, d, b1, b2, step, rbc2, decay, eps), o,
+                  n, STATE_GRID, s);
+  });
 }
 void mv_launch_adam_f64(double* d, double* m, double* v, const double* x,
                         double b1, double b2, double step, double rbc2,
                         double decay, double eps, int64_t n, hipStream_t s) {
   launch_elem<false>(adam_op(d, m, v, x, b1, b2, step, rbc2, decay, eps),
-                     nullptr, n, STATE_GRID, BLOCK, s);
+                     (double*)nullptr, n, STATE_GRID, BLOCK, s);
 }
 
 }  // extern "C"
@@ -428,22 +550,27 @@ void mv_launch_adam_f64(double* d, double* m, double* v, const double* x,
 // faster for scattered few-column rows.
 // ---------------------------------------------------------------------------
 
-// V = float, float2 or float4 column groups; total and cols count V's.
-template <class V, class Idx>
-__global__ void k_row_gather(V* __restrict__ out, const V* __restrict__ shard,
+// V = float, float2 or float4 column groups; total and cols count V's. O is
+// out's element type: float, or bf16 (each group narrowed as it is stored).
+template <class V, class O, class Idx>
+__global__ void k_row_gather(O* __restrict__ out, const V* __restrict__ shard,
                              const int64_t* __restrict__ rows,
                              Idx total, Idx cols) {
   Idx stride = (Idx)gridDim.x * blockDim.x;
   for (Idx i = (Idx)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += stride) {
     Idx r = i / cols, c = i - r * cols;
-    out[i] = shard[rows[r] * (int64_t)cols + c];
+    V v = shard[rows[r] * (int64_t)cols + c];
+    if constexpr (std::is_same<O, bf16>::value) st(out, i, v);
+    else ((V*)out)[i] = v;
   }
 }
 
-template <class Idx, bool ATOMIC>
+// D is vals' element type in the three keyed update kernels below: float,
+// or bf16 (widened per element; sums and atomics stay fp32).
+template <class D, class Idx, bool ATOMIC>
 __global__ void k_row_scatter_add(float* __restrict__ shard,
-                                  const float* __restrict__ vals,
+                                  const D* __restrict__ vals,
                                   const int64_t* __restrict__ rows,
                                   float sign, Idx total, Idx cols) {
   Idx stride = (Idx)gridDim.x * blockDim.x;
@@ -451,8 +578,9 @@ __global__ void k_row_scatter_add(float* __restrict__ shard,
        i += stride) {
     Idx r = i / cols, c = i - r * cols;
     int64_t k = rows[r] * (int64_t)cols + c;
-    if (ATOMIC) atomicAdd(&shard[k], sign * vals[i]);
-    else shard[k] += sign * vals[i];
+    float x = ld<float>(vals, i);
+    if (ATOMIC) atomicAdd(&shard[k], sign * x);
+    else shard[k] += sign * x;
   }
 }
 
@@ -461,10 +589,10 @@ __global__ void k_row_scatter_add(float* __restrict__ shard,
 // the LogisticRegression sparse path (BASELINE config: 1e9 sparse
 // features, AdaGrad updater). Duplicate rows race benignly (hogwild):
 // G accumulates via atomicAdd; the weight step uses the post-add G.
-template <class Idx, bool ATOMIC>
+template <class D, class Idx, bool ATOMIC>
 __global__ void k_row_scatter_adagrad(float* __restrict__ shard,
                                       float* __restrict__ gsq,
-                                      const float* __restrict__ vals,
+                                      const D* __restrict__ vals,
                                       const int64_t* __restrict__ rows,
                                       float inv_lr, float rho, float eps,
                                       Idx total, Idx cols) {
@@ -473,7 +601,7 @@ __global__ void k_row_scatter_adagrad(float* __restrict__ shard,
        i += stride) {
     Idx r = i / cols, c = i - r * cols;
     int64_t k = rows[r] * (int64_t)cols + c;
-    float g = vals[i] * inv_lr;
+    float g = ld<float>(vals, i) * inv_lr;
     if (g != 0.0f) {
       float G;
       if (ATOMIC) G = atomicAdd(&gsq[k], g * g) + g * g;
@@ -504,8 +632,8 @@ __global__ void k_row_scatter_adagrad(float* __restrict__ shard,
 // Known limit: one thread group sums all occurrences of a row serially, so
 // a row listed thousands of times in one batch stretches the launch to the
 // length of that run. Splitting long runs is not done here.
-template <class Op, class V, class Idx>
-__global__ void k_row_update(Op op, const float* __restrict__ vals,
+template <class Op, class V, class Idx, class D>
+__global__ void k_row_update(Op op, const D* __restrict__ vals,
                              const int64_t* __restrict__ rows,
                              const int64_t* __restrict__ perm, int64_t n,
                              Idx total, Idx cols) {
@@ -526,129 +654,96 @@ __global__ void k_row_update(Op op, const float* __restrict__ vals,
 static inline bool aligned16(const void* p) {
   return ((uintptr_t)p & 15) == 0;
 }
+// what V = v4f asks of vals: 16 bytes for fp32, 8 for bf16
+static inline bool vals_vec_ok(const float* p) { return aligned16(p); }
+static inline bool vals_vec_ok(const bf16* p) { return vec_ok(p); }
 
-// `vec` (decided by the caller from cols % 4 and the 16-byte alignment of
-// every pointer the op and the kernel touch) selects V = v4f. Geometry is
+// `vec` (decided by the caller from cols % 4 and the alignment of every
+// pointer the op and the kernel touch) selects V = v4f. Geometry is
 // the other row kernels' BLOCK x grid_for(total); no grid sweep has been
 // run for this shape. The 32-bit index form also needs room for the last
 // grid stride, so that i += stride cannot wrap.
-template <class Op>
-static void launch_row_update(const Op& op, bool vec, const float* vals,
+template <class Op, class D>
+static void launch_row_update(const Op& op, bool vec, const D* vals,
                               const int64_t* rows, const int64_t* perm,
                               int64_t n, int64_t cols, hipStream_t s) {
   if (!n || !cols) return;
+  vec = vec && cols % 4 == 0 && vals_vec_ok(vals);
   int64_t vcols = vec ? cols / 4 : cols, total = n * vcols;
   int grid = grid_for(total);
   bool narrow = total <= (int64_t)UINT32_MAX - (int64_t)MAX_GRID * BLOCK;
   if (vec && narrow)
-    k_row_update<Op, v4f, uint32_t><<<grid, BLOCK, 0, s>>>(
+    k_row_update<Op, v4f, uint32_t, D><<<grid, BLOCK, 0, s>>>(
         op, vals, rows, perm, n, (uint32_t)total, (uint32_t)vcols);
   else if (vec)
-    k_row_update<Op, v4f, int64_t><<<grid, BLOCK, 0, s>>>(
+    k_row_update<Op, v4f, int64_t, D><<<grid, BLOCK, 0, s>>>(
         op, vals, rows, perm, n, total, vcols);
   else if (narrow)
-    k_row_update<Op, float, uint32_t><<<grid, BLOCK, 0, s>>>(
+    k_row_update<Op, float, uint32_t, D><<<grid, BLOCK, 0, s>>>(
         op, vals, rows, perm, n, (uint32_t)total, (uint32_t)vcols);
   else
-    k_row_update<Op, float, int64_t><<<grid, BLOCK, 0, s>>>(
+    k_row_update<Op, float, int64_t, D><<<grid, BLOCK, 0, s>>>(
         op, vals, rows, perm, n, total, vcols);
 }
 
-extern "C" {
-
-void mv_launch_row_momentum(float* shard, float* m, const float* vals,
-                            const int64_t* rows, const int64_t* perm,
-                            float mu, int64_t nrows, int64_t cols,
-                            hipStream_t s) {
-  bool vec = cols % 4 == 0 && aligned16(shard) && aligned16(m) &&
-             aligned16(vals);
-  launch_row_update(MomentumOp<float>{shard, m, nullptr, mu}, vec, vals, rows,
-                    perm, nrows, cols, s);
-}
-
-void mv_launch_row_dcasgd(float* shard, float* bak, const float* vals,
-                          const int64_t* rows, const int64_t* perm, float lr,
-                          float lambda, int64_t nrows, int64_t cols,
-                          hipStream_t s) {
-  bool vec = cols % 4 == 0 && aligned16(shard) && aligned16(bak) &&
-             aligned16(vals);
-  launch_row_update(DcasgdOp{shard, bak, nullptr, lr, lambda}, vec, vals,
-                    rows, perm, nrows, cols, s);
-}
-
-void mv_launch_row_dcasgda(float* shard, float* bak, float* msq,
-                           const float* vals, const int64_t* rows,
-                           const int64_t* perm, float lr, float lambda,
-                           float rho, float eps, int64_t nrows, int64_t cols,
-                           hipStream_t s) {
-  bool vec = cols % 4 == 0 && aligned16(shard) && aligned16(bak) &&
-             aligned16(msq) && aligned16(vals);
-  launch_row_update(DcasgdaOp{shard, bak, msq, nullptr, lr, lambda, rho, eps},
-                    vec, vals, rows, perm, nrows, cols, s);
-}
-
-void mv_launch_row_adam(float* shard, float* m, float* v, const float* vals,
-                        const int64_t* rows, const int64_t* perm, double b1,
-                        double b2, double step, double rbc2, double decay,
-                        double eps, int64_t nrows, int64_t cols,
-                        hipStream_t s) {
-  bool vec = cols % 4 == 0 && aligned16(shard) && aligned16(m) &&
-             aligned16(v) && aligned16(vals);
-  launch_row_update(adam_op<float>(shard, m, v, nullptr, b1, b2, step, rbc2,
-                                   decay, eps),
-                    vec, vals, rows, perm, nrows, cols, s);
-}
-
-void mv_launch_row_gather(float* out, const float* shard, const int64_t* rows,
-                          int64_t nrows, int64_t cols, hipStream_t s) {
+// Column groups of 4, 2 or 1 by cols; a bf16 out also needs the group's
+// store alignment (8 or 4 bytes), an fp32 out is a 16-byte torch allocation.
+template <class O>
+static void launch_row_gather(O* out, const float* shard, const int64_t* rows,
+                              int64_t nrows, int64_t cols, hipStream_t s) {
   if (!nrows || !cols) return;
   int64_t total = nrows * cols;
-  if (cols % 4 == 0 && total / 4 <= UINT32_MAX) {
-    k_row_gather<float4, uint32_t><<<grid_for(total / 4), BLOCK, 0, s>>>(
-        (float4*)out, (const float4*)shard, rows, (uint32_t)(total / 4),
+  constexpr bool narrow_out = std::is_same<O, bf16>::value;
+  bool g4 = cols % 4 == 0 && (!narrow_out || ((uintptr_t)out & 7) == 0);
+  bool g2 = cols % 2 == 0 && (!narrow_out || ((uintptr_t)out & 3) == 0);
+  if (g4 && total / 4 <= UINT32_MAX) {
+    k_row_gather<float4, O, uint32_t><<<grid_for(total / 4), BLOCK, 0, s>>>(
+        out, (const float4*)shard, rows, (uint32_t)(total / 4),
         (uint32_t)(cols / 4));
-  } else if (cols % 4 == 0) {
-    k_row_gather<float4, int64_t><<<grid_for(total / 4), BLOCK, 0, s>>>(
-        (float4*)out, (const float4*)shard, rows, total / 4, cols / 4);
-  } else if (cols % 2 == 0 && total / 2 <= UINT32_MAX) {
-    k_row_gather<float2, uint32_t><<<grid_for(total / 2), BLOCK, 0, s>>>(
-        (float2*)out, (const float2*)shard, rows, (uint32_t)(total / 2),
+  } else if (g4) {
+    k_row_gather<float4, O, int64_t><<<grid_for(total / 4), BLOCK, 0, s>>>(
+        out, (const float4*)shard, rows, total / 4, cols / 4);
+  } else if (g2 && total / 2 <= UINT32_MAX) {
+    k_row_gather<float2, O, uint32_t><<<grid_for(total / 2), BLOCK, 0, s>>>(
+        out, (const float2*)shard, rows, (uint32_t)(total / 2),
         (uint32_t)(cols / 2));
   } else if (total <= UINT32_MAX) {
-    k_row_gather<float, uint32_t><<<grid_for(total), BLOCK, 0, s>>>(
+    k_row_gather<float, O, uint32_t><<<grid_for(total), BLOCK, 0, s>>>(
         out, shard, rows, (uint32_t)total, (uint32_t)cols);
   } else {
-    k_row_gather<float, int64_t><<<grid_for(total), BLOCK, 0, s>>>(
+    k_row_gather<float, O, int64_t><<<grid_for(total), BLOCK, 0, s>>>(
         out, shard, rows, total, cols);
   }
 }
 
-void mv_launch_row_scatter_add(float* shard, const float* vals,
-                               const int64_t* rows, float sign,
-                               int64_t nrows, int64_t cols,
-                               int assume_unique, hipStream_t s) {
+template <class D>
+static void launch_row_scatter_add(float* shard, const D* vals,
+                                   const int64_t* rows, float sign,
+                                   int64_t nrows, int64_t cols,
+                                   int assume_unique, hipStream_t s) {
   if (!nrows || !cols) return;
   int64_t total = nrows * cols;
   int grid = grid_for(total);
   if (total <= UINT32_MAX) {
     uint32_t t = (uint32_t)total, c = (uint32_t)cols;
     if (assume_unique)
-      k_row_scatter_add<uint32_t, false><<<grid, BLOCK, 0, s>>>(
+      k_row_scatter_add<D, uint32_t, false><<<grid, BLOCK, 0, s>>>(
           shard, vals, rows, sign, t, c);
     else
-      k_row_scatter_add<uint32_t, true><<<grid, BLOCK, 0, s>>>(
+      k_row_scatter_add<D, uint32_t, true><<<grid, BLOCK, 0, s>>>(
           shard, vals, rows, sign, t, c);
   } else if (assume_unique) {
-    k_row_scatter_add<int64_t, false><<<grid, BLOCK, 0, s>>>(
+    k_row_scatter_add<D, int64_t, false><<<grid, BLOCK, 0, s>>>(
         shard, vals, rows, sign, total, cols);
   } else {
-    k_row_scatter_add<int64_t, true><<<grid, BLOCK, 0, s>>>(
+    k_row_scatter_add<D, int64_t, true><<<grid, BLOCK, 0, s>>>(
         shard, vals, rows, sign, total, cols);
   }
 }
 
-void mv_launch_row_scatter_adagrad(
-    float* shard, float* gsq, const float* vals, const int64_t* rows,
+template <class D>
+static void launch_row_scatter_adagrad(
+    float* shard, float* gsq, const D* vals, const int64_t* rows,
     float lr, float rho, float eps, int64_t nrows, int64_t cols,
     int assume_unique, hipStream_t s) {
   if (!nrows || !cols) return;
@@ -658,18 +753,98 @@ void mv_launch_row_scatter_adagrad(
   if (total <= UINT32_MAX) {
     uint32_t t = (uint32_t)total, c = (uint32_t)cols;
     if (assume_unique)
-      k_row_scatter_adagrad<uint32_t, false><<<grid, BLOCK, 0, s>>>(
+      k_row_scatter_adagrad<D, uint32_t, false><<<grid, BLOCK, 0, s>>>(
           shard, gsq, vals, rows, inv_lr, rho, eps, t, c);
     else
-      k_row_scatter_adagrad<uint32_t, true><<<grid, BLOCK, 0, s>>>(
+      k_row_scatter_adagrad<D, uint32_t, true><<<grid, BLOCK, 0, s>>>(
           shard, gsq, vals, rows, inv_lr, rho, eps, t, c);
   } else if (assume_unique) {
-    k_row_scatter_adagrad<int64_t, false><<<grid, BLOCK, 0, s>>>(
+    k_row_scatter_adagrad<D, int64_t, false><<<grid, BLOCK, 0, s>>>(
         shard, gsq, vals, rows, inv_lr, rho, eps, total, cols);
   } else {
-    k_row_scatter_adagrad<int64_t, true><<<grid, BLOCK, 0, s>>>(
+    k_row_scatter_adagrad<D, int64_t, true><<<grid, BLOCK, 0, s>>>(
         shard, gsq, vals, rows, inv_lr, rho, eps, total, cols);
   }
+}
+
+extern "C" {
+
+// In the keyed launchers `vals` (and the gather's `out`) is void* plus the
+// WIRE_* bit that says whether it holds bf16, as in the elementwise ones.
+void mv_launch_row_momentum(float* shard, float* m, const void* vals, int wire,
+                            const int64_t* rows, const int64_t* perm,
+                            float mu, int64_t nrows, int64_t cols,
+                            hipStream_t s) {
+  bool vec = aligned16(shard) && aligned16(m);
+  with_wire(wire, vals, nullptr, [&](auto* x, auto*) {
+    launch_row_update(MomentumOp<float>{shard, m, nullptr, mu}, vec, x, rows,
+                      perm, nrows, cols, s);
+  });
+}
+
+void mv_launch_row_dcasgd(float* shard, float* bak, const void* vals, int wire,
+                          const int64_t* rows, const int64_t* perm, float lr,
+                          float lambda, int64_t nrows, int64_t cols,
+                          hipStream_t s) {
+  bool vec = aligned16(shard) && aligned16(bak);
+  with_wire(wire, vals, nullptr, [&](auto* x, auto*) {
+    launch_row_update(DcasgdOp<float>{shard, bak, nullptr, lr, lambda}, vec,
+                      x, rows, perm, nrows, cols, s);
+  });
+}
+
+void mv_launch_row_dcasgda(float* shard, float* bak, float* msq,
+                           const void* vals, int wire, const int64_t* rows,
+                           const int64_t* perm, float lr, float lambda,
+                           float rho, float eps, int64_t nrows, int64_t cols,
+                           hipStream_t s) {
+  bool vec = aligned16(shard) && aligned16(bak) && aligned16(msq);
+  with_wire(wire, vals, nullptr, [&](auto* x, auto*) {
+    launch_row_update(DcasgdaOp<float>{shard, bak, msq, nullptr, lr, lambda,
+                                       rho, eps},
+                      vec, x, rows, perm, nrows, cols, s);
+  });
+}
+
+void mv_launch_row_adam(float* shard, float* m, float* v, const void* vals,
+                        int wire, const int64_t* rows, const int64_t* perm,
+                        double b1, double b2, double step, double rbc2,
+                        double decay, double eps, int64_t nrows, int64_t cols,
+                        hipStream_t s) {
+  bool vec = aligned16(shard) && aligned16(m) && aligned16(v);
+  with_wire(wire, vals, nullptr, [&](auto* x, auto*) {
+    launch_row_update(adam_op<float, float>(shard, m, v, nullptr, b1, b2,
+                                            step, rbc2, decay, eps),
+                      vec, x, rows, perm, nrows, cols, s);
+  });
+}
+
+void mv_launch_row_gather(void* out, int wire, const float* shard,
+                          const int64_t* rows, int64_t nrows, int64_t cols,
+                          hipStream_t s) {
+  with_wire(wire, nullptr, out, [&](auto*, auto* o) {
+    launch_row_gather(o, shard, rows, nrows, cols, s);
+  });
+}
+
+void mv_launch_row_scatter_add(float* shard, const void* vals, int wire,
+                               const int64_t* rows, float sign,
+                               int64_t nrows, int64_t cols,
+                               int assume_unique, hipStream_t s) {
+  with_wire(wire, vals, nullptr, [&](auto* x, auto*) {
+    launch_row_scatter_add(shard, x, rows, sign, nrows, cols, assume_unique,
+                           s);
+  });
+}
+
+void mv_launch_row_scatter_adagrad(
+    float* shard, float* gsq, const void* vals, int wire, const int64_t* rows,
+    float lr, float rho, float eps, int64_t nrows, int64_t cols,
+    int assume_unique, hipStream_t s) {
+  with_wire(wire, vals, nullptr, [&](auto* x, auto*) {
+    launch_row_scatter_adagrad(shard, gsq, x, rows, lr, rho, eps, nrows, cols,
+                               assume_unique, s);
+  });
 }
 
 }  // extern "C"

@@ -10,6 +10,11 @@ copy-out on Get (:130-141), raw-bytes Store/Load (:144-151).
 MI355X mapping: Get = all-gather of shards into the caller's buffer;
 Add = reduce-scatter of the delta followed by one fused updater kernel on
 the owned shard. Both can be issued async and overlap with compute.
+
+``wire_dtype=torch.bfloat16`` (float32 tables) halves the bytes of both: the
+delta is rounded to bf16 once and travels so, the owner's updater kernel
+widens it in registers, and Get returns the fp32 shard rounded to bf16. The
+shard, updater state and Store/Load stay fp32.
 """
 
 from __future__ import annotations
@@ -27,8 +32,10 @@ from .base import Table
 
 class ArrayTable(Table):
     def __init__(self, size: int, dtype: torch.dtype = torch.float32,
-                 updater_type: Optional[str] = None) -> None:
+                 updater_type: Optional[str] = None,
+                 wire_dtype: Optional[torch.dtype] = None) -> None:
         super().__init__(updater_type)
+        self._set_wire(wire_dtype, dtype)
         CHECK(size >= self.zoo.num_servers,
               f"table size {size} must be >= num_servers "
               f"{self.zoo.num_servers} (reference array_table.cpp:14)")
@@ -74,13 +81,14 @@ class ArrayTable(Table):
             self._deferred = None
             self._check_deferred(d)
             if out is None:
-                out = torch.empty(self.size, dtype=self.dtype,
+                out = torch.empty(self.size, dtype=self.wire,
                                   device=self.device)
             CHECK(out.numel() == self.size, "Get buffer size mismatch")
-            # fused update+copy kernel needs a GPU fp32 contiguous target
-            # (see matrix_table.get); anything else materializes the Add
+            # fused update+copy kernel needs a GPU contiguous target of the
+            # wire dtype (see matrix_table.get); anything else materializes
+            # the Add
             if (out.is_contiguous() and out.is_cuda
-                    and out.dtype == self.dtype):
+                    and out.dtype == self.wire):
                 with monitor("server.update"):
                     self.updater.update_and_copy(d[0], d[1], out.view(-1))
                 return out
@@ -89,10 +97,10 @@ class ArrayTable(Table):
         self.flush()
         user_out = out
         if out is None:
-            out = torch.empty(self.size, dtype=self.dtype, device=self.device)
+            out = torch.empty(self.size, dtype=self.wire, device=self.device)
         CHECK(out.numel() == self.size, "Get buffer size mismatch")
-        if not out.is_contiguous():
-            out = torch.empty(self.size, dtype=self.dtype, device=self.device)
+        if not out.is_contiguous() or self._stage_get(out):
+            out = torch.empty(self.size, dtype=self.wire, device=self.device)
         with monitor("worker.get"):
             h = allgather_shards(out.view(-1), self.shard, self.spec, 1,
                                  async_op=async_op)
@@ -112,8 +120,8 @@ class ArrayTable(Table):
         CHECK(self.zoo.is_worker, "ps_role=server ranks issue no Gets")
         self.flush()
         user_out = out
-        if out is None or not out.is_contiguous():
-            out = torch.empty(self.size, dtype=self.dtype,
+        if out is None or not out.is_contiguous() or self._stage_get(out):
+            out = torch.empty(self.size, dtype=self.wire,
                               device=self.device)
         CHECK(out.numel() == self.size, "Get buffer size mismatch")
         with monitor("worker.get"):
@@ -136,7 +144,7 @@ class ArrayTable(Table):
         array_table.cpp:116-127); in async mode, per-server slices
         applied on arrival."""
         CHECK(delta.numel() == self.size, "Add delta size mismatch")
-        delta = delta.to(self.device, self.dtype).contiguous().view(-1)
+        delta = delta.to(self.device, self.wire).contiguous().view(-1)
         eng = self.engine
         if eng is not None:
             CHECK(self.zoo.is_worker, "ps_role=server ranks issue no Adds")

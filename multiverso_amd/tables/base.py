@@ -23,7 +23,7 @@ from typing import List, Optional
 
 import torch
 
-from ..comm import Handle
+from ..comm import Handle, narrow_shard
 from ..log import CHECK
 from ..updaters import AddOption, create_updater
 from ..zoo import Zoo
@@ -48,6 +48,9 @@ class Table:
             updater_type = get_flag("updater_type")
         self.updater_type = updater_type
         self.updater = None  # created by subclass once the shard exists
+        # dtype of Add/Get payloads; tables that take ``wire_dtype`` set it
+        # (_set_wire), None means the shard's own dtype
+        self.wire: Optional[torch.dtype] = None
         # async mode: a fast worker's request can arrive before THIS
         # rank finished constructing the table (the reference's
         # RegisterTable round-trip subsumed this); the server thread
@@ -68,15 +71,45 @@ class Table:
     # ---- server-side entry points (ServerTable::ProcessAdd/ProcessGet,
     # table_interface.h:61-75) — called by the async server thread AND by
     # local worker fast paths; both hold the shard lock ----
+    def _set_wire(self, wire_dtype: Optional[torch.dtype],
+                  dtype: torch.dtype) -> None:
+        """Resolve the ``wire_dtype`` keyword: None or the table's own dtype
+        keep payloads in that dtype; bfloat16 on a float32 table is the
+        half-width wire (fp32 shard and updater state, bf16 Add deltas and
+        Get results)."""
+        if wire_dtype is None or wire_dtype == dtype:
+            self.wire = dtype
+        elif wire_dtype == torch.bfloat16 and dtype == torch.float32:
+            self.wire = torch.bfloat16
+        else:
+            raise TypeError(f"wire_dtype {wire_dtype} is not supported on a "
+                            f"{dtype} table (torch.bfloat16 needs a float32 "
+                            f"table; None keeps the table's dtype)")
+
+    def _stage_get(self, out: torch.Tensor) -> bool:
+        """bf16 wire only: a Get buffer of another dtype (fp32, say) is
+        filled through a bf16 staging buffer and torch ``copy_``, so the
+        caller sees the same bf16-rounded values whatever the world size."""
+        return self.wire != self.updater.shard.dtype and out.dtype != self.wire
+
     def _server_apply_chunk(self, chunk: torch.Tensor, option) -> None:
         with self._shard_lock:
-            self.updater.update(
-                chunk.to(self.updater.shard.device,
-                         self.updater.shard.dtype), option)
+            shard = self.updater.shard
+            # a bf16-wire chunk stays bf16: the updater widens it
+            dt = chunk.dtype if chunk.dtype == self.wire else shard.dtype
+            self.updater.update(chunk.to(shard.device, dt), option)
 
     def _server_read_chunk_into(self, out_flat: torch.Tensor) -> None:
         with self._shard_lock:
             src = self.updater.shard.view(-1)
+            if (out_flat.dtype == torch.bfloat16
+                    and src.dtype == torch.float32 and src.is_cuda):
+                # bf16 wire: narrow on the GPU, so a host-staged reply
+                # crosses PCIe at half size
+                if out_flat.device == src.device:
+                    narrow_shard(src, out_flat.dtype, out=out_flat)
+                    return
+                src = narrow_shard(src, out_flat.dtype)
             if out_flat.device == src.device:
                 out_flat.copy_(src)
             else:

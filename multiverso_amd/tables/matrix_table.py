@@ -21,8 +21,15 @@ MI355X mapping:
   step per distinct row; weights and updater state of other rows stay as
   they are.
 
+- ``wire_dtype=torch.bfloat16`` (float32 tables): every payload above is
+  bf16 — whole-table deltas and Get results, keyed values in both directions
+  of the all-to-all — while the shard and updater state stay fp32. The
+  kernels widen and narrow in registers; duplicate rows of a keyed Add are
+  summed in fp32 after widening.
+
 Sparse/stale-aware Get (SparseMatrixTable's per-(worker,row) freshness
-bitmap) is implemented in sparse_matrix.py on top of this class.
+bitmap) is implemented in sparse_matrix.py on top of this class; it takes no
+``wire_dtype``.
 """
 
 from __future__ import annotations
@@ -43,8 +50,10 @@ class MatrixTable(Table):
     def __init__(self, num_row: int, num_col: int,
                  dtype: torch.dtype = torch.float32,
                  updater_type: Optional[str] = None,
-                 random_init: Optional[Tuple[float, float]] = None) -> None:
+                 random_init: Optional[Tuple[float, float]] = None,
+                 wire_dtype: Optional[torch.dtype] = None) -> None:
         super().__init__(updater_type)
+        self._set_wire(wire_dtype, dtype)
         CHECK(num_row >= self.zoo.num_servers,
               f"num_row {num_row} must be >= num_servers")
         self.num_row = num_row
@@ -100,8 +109,8 @@ class MatrixTable(Table):
         CHECK(self.zoo.is_worker, "ps_role=server ranks issue no Gets")
         self.flush()
         user_out = out
-        if out is None or not out.is_contiguous():
-            out = torch.empty(self.num_row, self.num_col, dtype=self.dtype,
+        if out is None or not out.is_contiguous() or self._stage_get(out):
+            out = torch.empty(self.num_row, self.num_col, dtype=self.wire,
                               device=self.device)
         CHECK(out.numel() == self.num_row * self.num_col,
               "Get buffer size mismatch")
@@ -129,14 +138,15 @@ class MatrixTable(Table):
             self._check_deferred(d)
             if out is None:
                 out = torch.empty(self.num_row, self.num_col,
-                                  dtype=self.dtype, device=self.device)
+                                  dtype=self.wire, device=self.device)
             CHECK(out.numel() == self.num_row * self.num_col,
                   "Get buffer size mismatch")
-            # fused update+copy kernel needs a GPU fp32 contiguous target
-            # (the deferral itself only happens on GPU shards); any other
-            # out materializes the Add and falls through to the copy path
+            # fused update+copy kernel needs a GPU contiguous target of the
+            # wire dtype (fp32, or bf16 on a bf16-wire table; the deferral
+            # itself only happens on GPU shards); any other out materializes
+            # the Add and falls through to the copy path
             if (out.is_contiguous() and out.is_cuda
-                    and out.dtype == self.dtype):
+                    and out.dtype == self.wire):
                 with monitor("server.update"):
                     self.updater.update_and_copy(d[0], d[1], out.view(-1))
                 return out
@@ -145,14 +155,14 @@ class MatrixTable(Table):
         self.flush()
         user_out = out
         if out is None:
-            out = torch.empty(self.num_row, self.num_col, dtype=self.dtype,
+            out = torch.empty(self.num_row, self.num_col, dtype=self.wire,
                               device=self.device)
         CHECK(out.numel() == self.num_row * self.num_col,
               "Get buffer size mismatch")
-        if not out.is_contiguous():
-            # gather needs a flat view; stage and copy into the user's
-            # strided buffer afterwards
-            out = torch.empty(self.num_row, self.num_col, dtype=self.dtype,
+        if not out.is_contiguous() or self._stage_get(out):
+            # gather needs a flat view (and, on a bf16-wire table, a bf16
+            # one); stage and copy into the user's buffer afterwards
+            out = torch.empty(self.num_row, self.num_col, dtype=self.wire,
                               device=self.device)
         with monitor("worker.get"):
             h = allgather_shards(out.view(-1), self.shard.view(-1), self.spec,
@@ -176,7 +186,7 @@ class MatrixTable(Table):
         materialization (e.g. before timing the update itself)."""
         CHECK(delta.numel() == self.num_row * self.num_col,
               "Add delta size mismatch")
-        delta = delta.to(self.device, self.dtype).contiguous().view(-1)
+        delta = delta.to(self.device, self.wire).contiguous().view(-1)
         eng = self.engine
         if eng is not None:
             CHECK(self.zoo.is_worker, "ps_role=server ranks issue no Adds")
@@ -216,8 +226,11 @@ class MatrixTable(Table):
         other dtypes use torch indexing — parity, not headline)."""
         if self.shard.is_cuda and self.dtype == torch.float32:
             from .. import ops
-            return ops.module(required=True).row_gather(self.shard, local_ids)
-        return self.shard[local_ids]
+            hip = ops.module(required=True)
+            if self.wire != self.dtype:   # bf16 wire: narrow while gathering
+                return hip.row_gather(self.shard, local_ids, self.wire)
+            return hip.row_gather(self.shard, local_ids)
+        return self.shard[local_ids].to(self.wire)
 
     def _scatter_update_local(self, local_ids: torch.Tensor,
                               vals: torch.Tensor,
@@ -244,9 +257,13 @@ class MatrixTable(Table):
                              dtype=torch.float64, device=v.device)
             torch.cumsum(v.to(torch.float64), 0, out=cs[1:])
             ends = counts.cumsum(0)
-            agg = (cs[ends] - cs[ends - counts]).to(v.dtype)
+            # the table's dtype, not v's: a bf16-wire sum stays fp32
+            agg = (cs[ends] - cs[ends - counts]).to(self.dtype)
             local_ids, vals = uids, agg.reshape(-1)
             assume_unique = True
+        if not self.shard.is_cuda:
+            # CPU fallback of the bf16 wire: torch ops on the widened values
+            vals = vals.to(self.dtype)
         if self.updater_type == "adagrad":
             from ..updaters import AddOption as _AO
             opt = option or _AO()
@@ -394,7 +411,7 @@ class MatrixTable(Table):
                 # identity index_put (measured, profiles r2 smaxprof2)
                 return served.view(-1, self.num_col)
             # got is in owner-grouped order == order of sorted ids; undo sort
-            out = torch.empty(ids.numel(), self.num_col, dtype=self.dtype,
+            out = torch.empty(ids.numel(), self.num_col, dtype=self.wire,
                               device=self.device)
             out[order] = got
         return out
@@ -409,7 +426,7 @@ class MatrixTable(Table):
         still collide across ranks, so atomics stay."""
         self.flush()   # a deferred whole-table Add must land first
         ids = torch.as_tensor(row_ids, dtype=torch.int64)
-        vals = values.to(self.device, self.dtype).contiguous()
+        vals = values.to(self.device, self.wire).contiguous()
         CHECK(vals.numel() == ids.numel() * self.num_col,
               "add_rows values size mismatch")
         eng = self.engine

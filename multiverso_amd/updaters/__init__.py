@@ -40,6 +40,14 @@ kernels, float4-vectorized, grid-stride (memory-bound per the CDNA4 guide:
 the bound is HBM3E bytes, so fusing m/G state updates into the same pass
 halves traffic vs. composing torch ops). CPU fallback uses torch ops and
 is numerically identical in fp32.
+
+bf16 wire format (tables built with ``wire_dtype=torch.bfloat16``): on a
+float32 shard every updater also takes a bfloat16 ``delta``, and
+``update_and_copy`` a bfloat16 ``out``. The shard and all state stay fp32.
+The HIP kernels widen the delta and narrow the Get buffer (round to nearest
+even, bit for bit torch's cast) in registers, so no fp32 copy of the delta
+exists on the GPU path; the CPU fallback runs the same torch ops on
+``delta.float()``.
 """
 
 from __future__ import annotations
@@ -85,6 +93,11 @@ class AddOption:
         return cls(worker_id, beta1, lr, beta2, weight_decay)
 
 
+def _widened(delta: torch.Tensor) -> torch.Tensor:
+    """CPU fallback of the bf16 wire: the delta as fp32 (exact)."""
+    return delta.float() if delta.dtype == torch.bfloat16 else delta
+
+
 def _hip_ops():
     """In-tree HIP extension, or None on CPU-only hosts. On a GPU host a
     missing extension is a hard error (no silent eager fallback)."""
@@ -102,7 +115,7 @@ class Updater:
         if self.shard.is_cuda:
             _hip_ops().add_inplace(self.shard, delta)
         else:
-            self.shard.add_(delta)
+            self.shard.add_(_widened(delta))
 
     def update_and_copy(self, delta: torch.Tensor,
                         option: Optional[AddOption],
@@ -130,7 +143,7 @@ class SGDUpdater(Updater):
         if self.shard.is_cuda:
             _hip_ops().sgd_update(self.shard, delta)
         else:
-            self.shard.sub_(delta)
+            self.shard.sub_(_widened(delta))
 
     def update_and_copy(self, delta, option, out) -> None:
         if self.shard.is_cuda and self.shard.dtype in (torch.float32,
@@ -154,7 +167,8 @@ class MomentumUpdater(Updater):
             _hip_ops().momentum_update(self.shard, self.smooth_gradient,
                                        delta, float(mu))
         else:
-            self.smooth_gradient.mul_(mu).add_(delta, alpha=1.0 - mu)
+            self.smooth_gradient.mul_(mu).add_(_widened(delta),
+                                               alpha=1.0 - mu)
             self.shard.sub_(self.smooth_gradient)
 
     def update_and_copy(self, delta, option, out) -> None:
@@ -182,7 +196,7 @@ class AdaGradUpdater(Updater):
             _hip_ops().adagrad_update(self.shard, self.g_sqr, delta,
                                       float(lr), float(rho), self.EPS)
         else:
-            g = delta / lr
+            g = _widened(delta) / lr
             self.g_sqr.add_(g * g)
             self.shard.sub_(rho * g / torch.sqrt(self.g_sqr + self.EPS))
 
@@ -231,7 +245,7 @@ class DCASGDUpdater(Updater):
             _hip_ops().dcasgd_update(self.shard, bak, delta,
                                      float(lr), float(lam))
         else:
-            g = delta
+            g = _widened(delta)
             self.shard.sub_(lr * (g + lam * g * g * (self.shard - bak)))
             bak.copy_(self.shard)
 
@@ -268,7 +282,7 @@ class DCASGDAUpdater(DCASGDUpdater):
                                       float(lr), float(lam), float(rho),
                                       self.EPS)
         else:
-            g = delta
+            g = _widened(delta)
             self.mean_sqr.mul_(rho).add_((1.0 - rho) * g * g)
             lam_t = lam / torch.sqrt(self.mean_sqr + self.EPS)
             self.shard.sub_(lr * (g + lam_t * g * g * (self.shard - bak)))
@@ -352,8 +366,8 @@ class AdamUpdater(Updater):
             _hip_ops().adam_update(self.shard, self.exp_avg, self.exp_avg_sq,
                                    delta, *s)
         else:
-            self.torch_step(self.shard, self.exp_avg, self.exp_avg_sq, delta,
-                            s)
+            self.torch_step(self.shard, self.exp_avg, self.exp_avg_sq,
+                            _widened(delta), s)
 
     def update_and_copy(self, delta, option, out) -> None:
         if self.shard.is_cuda and self.shard.dtype == torch.float32:

@@ -5,6 +5,7 @@ prints the Dashboard.
 
 Run (CPU or GPU):  python tools/matrix_perf.py [--rows N] [--cols N]
                        [--updater momentum]   (times the keyed updater path)
+                       [--wire-dtype bf16]    (bf16 payloads, fp32 shard)
 Multi-rank:        python -m torch.distributed.run --nproc-per-node N \
                        --master-addr 127.0.0.1 tools/matrix_perf.py
 """
@@ -33,6 +34,9 @@ def main():
                             "dcasgd", "dcasgda", "adam"],
                    help="updater_type of the table; the keyed Adds carry a "
                         "matching AddOption")
+    p.add_argument("--wire-dtype", default="fp32", choices=["fp32", "bf16"],
+                   help="wire_dtype of the table: bf16 moves keyed values "
+                        "and Get results as bfloat16 over the fp32 shard")
     p.add_argument("--repeat", type=int, default=1,
                    help="time each keyed Add this many times after one "
                         "untimed warm-up and print the median (1: a single "
@@ -47,6 +51,8 @@ def main():
     args = p.parse_args()
     if args.torch_composed and (args.updater != "momentum" or args.sparse):
         p.error("--torch-composed needs --updater momentum without --sparse")
+    if args.wire_dtype == "bf16" and (args.sparse or args.torch_composed):
+        p.error("--wire-dtype bf16 needs a dense table and its own Add")
     if args.seed is not None:
         torch.manual_seed(args.seed)
 
@@ -57,11 +63,13 @@ def main():
     if device.type != "cuda":
         args.rows = min(args.rows, 50_000)
 
+    wire = torch.bfloat16 if args.wire_dtype == "bf16" else None
     if args.sparse:
         t = mv.SparseMatrixTable(args.rows, args.cols,
                                  updater_type=args.updater)
     else:
-        t = mv.MatrixTable(args.rows, args.cols, updater_type=args.updater)
+        t = mv.MatrixTable(args.rows, args.cols, updater_type=args.updater,
+                           wire_dtype=wire)
     option = None
     if args.updater == "momentum":
         option = mv.AddOption(momentum=0.9)
@@ -71,7 +79,8 @@ def main():
     elif args.updater == "adam":
         option = mv.AddOption.adam(lr=0.1, weight_decay=0.01,
                                    worker_id=mv.rank())
-    out = torch.empty(args.rows, args.cols, device=device)
+    # the worker holds its buffers in the wire dtype
+    out = torch.empty(args.rows, args.cols, device=device, dtype=t.wire)
 
     def timed(fn):
         mv.barrier()
@@ -110,7 +119,7 @@ def main():
     for pct in range(10, 101, 10):
         k = args.rows * pct // 100
         ids = rows_all[torch.randperm(args.rows, device=device)[:k]]
-        vals = torch.rand(k, args.cols, device=device)
+        vals = torch.rand(k, args.cols, device=device).to(t.wire)
         if args.sparse:
             got = [0]
 
