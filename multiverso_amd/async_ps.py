@@ -120,6 +120,8 @@ class AsyncEngine:
     #   [opt: 5 f64 if has_opt][keys: n_keys i64][vals: n_vals dtype]
     # Value payloads, of requests and replies alike, are in the table's wire
     # dtype (table.wire: the table's dtype, or bf16 on a bf16-wire table).
+    # The one exception is OP_ADD on a table built with add_filter="onebit":
+    # its vals section is the onebit_filter payload of the n_vals elements.
     def _send_request(self, dst: int, hdr_fields: List[int],
                       payloads: List[torch.Tensor]):
         """Returns (works, refs): pending isends + the buffers that must
@@ -149,12 +151,27 @@ class AsyncEngine:
         for s in range(table.spec.n):
             off, cnt = table.spec.range_of(s)
             dst = zoo.server_ranks[s]
-            piece = delta_flat[off * unit:(off + cnt) * unit]
-            if dst == zoo.rank:
+            lo, hi = off * unit, (off + cnt) * unit
+            piece = delta_flat[lo:hi]
+            if table.add_filter:
+                # 1-bit wire: the piece is encoded where the delta lives and
+                # the uint8 payload travels in the place of the values
+                # (n_vals keeps the element count); the piece this rank owns
+                # takes the same encode and decode, minus the transport
+                from . import onebit_filter
+                res = table._filter_residual(delta_flat.numel())
+                payload = onebit_filter.encode(piece, res[lo:hi])
+                if dst == zoo.rank:
+                    table._server_apply_chunk(
+                        onebit_filter.decode_sum(payload, hi - lo, 1), option)
+                    continue
+                payload = payload.cpu()
+            elif dst == zoo.rank:
                 table._server_apply_chunk(piece, option)
                 continue
-            payload = piece.cpu().contiguous()
-            hdr = [OP_ADD, table.table_id, 0, payload.numel(),
+            else:
+                payload = piece.cpu().contiguous()
+            hdr = [OP_ADD, table.table_id, 0, hi - lo,
                    1 if want_ack else 0, 0 if opt is None else 1]
             ps = ([] if opt is None else [opt]) + [payload]
             w, r = self._send_request(dst, hdr, ps)
@@ -469,6 +486,13 @@ class AsyncEngine:
         vals_bytes = (0 if vals_dtype is None
                       else n_vals * torch.empty(0, dtype=vals_dtype)
                                          .element_size())
+        onebit = bool(n_vals) and op == OP_ADD and bool(table.add_filter)
+        if onebit:
+            # 1-bit wire: n_vals counts elements, the blob carries their
+            # onebit_filter payload
+            from . import onebit_filter
+            vals_dtype = torch.uint8
+            vals_bytes = onebit_filter.payload_bytes(n_vals)
         nbytes = (40 if has_opt else 0) + n_keys * 8 + vals_bytes
         keys = None
         vals = None
@@ -488,7 +512,10 @@ class AsyncEngine:
 
         if op == OP_ADD:
             with monitor("server.process_add"):
-                table._server_apply_chunk(vals.to(table.device), option)
+                vals = vals.to(table.device)
+                if onebit:
+                    vals = onebit_filter.decode_sum(vals, n_vals, 1)
+                table._server_apply_chunk(vals, option)
             if want_ack:
                 dist.send(torch.zeros(1, dtype=torch.int64), src,
                           group=self.rep)

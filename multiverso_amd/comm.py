@@ -19,6 +19,9 @@ MI355X-native mapping (BASELINE.json north star):
   dtype-specific except the Get side, where the owner narrows its shard
   before the all-gather (``narrow_shard``). A reduce-scatter of bf16 deltas
   sums in bf16, with the backend's rounding.
+- 1-bit Add wire (tables built with ``add_filter="onebit"``): the whole-table
+  Add becomes an all-to-all of onebit_filter payloads, decoded and summed by
+  the owner (``onebit_exchange_delta``).
 
 Sharding parity: contiguous partition with ``total // n`` per server and
 the remainder on the last server — identical to ArrayTable
@@ -223,6 +226,52 @@ def reduce_scatter_delta(delta_flat: torch.Tensor, spec: ShardSpec, unit: int,
     work = dist.reduce_scatter_tensor(out, buf, op=dist.ReduceOp.SUM, async_op=async_op)
     out = out[:cnt * unit]
     return out, (Handle(work) if async_op else _NOOP)
+
+
+def onebit_exchange_delta(delta_flat: torch.Tensor, residual: torch.Tensor,
+                          spec: ShardSpec, unit: int, async_op: bool = False
+                          ) -> Tuple[torch.Tensor, Handle]:
+    """The whole-table Add of a table built with ``add_filter="onebit"``:
+    where ``reduce_scatter_delta`` moves ``4*size`` bytes per rank, this
+    moves about ``size/8``. Every rank encodes its delta piece by piece
+    (onebit_filter, one payload per owner, error feedback into ``residual``)
+    into one uint8 send buffer; one all-to-all delivers to each owner the
+    payloads of its own piece, one per source rank; the owner decodes and
+    sums them in rank order into the fp32 chunk it returns.
+
+    Send sizes differ per destination and every receive size is
+    ``payload_bytes`` of this rank's own piece; both follow from ``spec``, so
+    there is no size exchange, and uneven shards need no padding. Payload
+    offsets are multiples of 136, which keeps each 8-byte aligned. With
+    ``async_op`` the chunk is valid once the returned Handle has been waited
+    for (its epilogue decodes). Not called on a single rank: there the table
+    encodes and decodes without a transport."""
+    from . import onebit_filter
+    n, rank = dist.get_world_size(), dist.get_rank()
+    sizes = [onebit_filter.payload_bytes(c * unit) for c in spec.counts]
+    send = torch.empty(sum(sizes), dtype=torch.uint8,
+                       device=delta_flat.device)
+    at = 0
+    for r in range(n):
+        off, cnt = spec.range_of(r)
+        lo, hi = off * unit, (off + cnt) * unit
+        onebit_filter.encode(delta_flat[lo:hi], residual[lo:hi],
+                             out=send[at:at + sizes[r]])
+        at += sizes[r]
+    mine = spec.counts[rank] * unit
+    recv = torch.empty(n * sizes[rank], dtype=torch.uint8,
+                       device=delta_flat.device)
+    chunk = torch.empty(mine, dtype=torch.float32, device=delta_flat.device)
+    work = dist.all_to_all_single(recv, send, [sizes[rank]] * n, sizes,
+                                  async_op=async_op)
+
+    def epilogue(_keep=send) -> None:   # send outlives the collective
+        onebit_filter.decode_sum(recv, mine, n, out=chunk)
+
+    if async_op:
+        return chunk, Handle(work, epilogue)
+    epilogue()
+    return chunk, _NOOP
 
 
 def all_to_all_rows(row_ids: torch.Tensor, values: Optional[torch.Tensor],

@@ -43,6 +43,10 @@ void mv_launch_adam_f64(double*, double*, double*, const double*, double,
                         double, double, double, double, double, int64_t,
                         hipStream_t);
 // keyed kernels: `vals` (the gather's `out`) is void* followed by `wire`
+void mv_launch_onebit_encode(const float*, float*, uint8_t*, int64_t,
+                             hipStream_t);
+void mv_launch_onebit_decode_sum(float*, const uint8_t*, int, int64_t,
+                                 hipStream_t);
 void mv_launch_row_gather(void*, int, const float*, const int64_t*, int64_t,
                           int64_t, hipStream_t);
 void mv_launch_row_scatter_add(float*, const void*, int, const int64_t*, float,
@@ -329,6 +333,42 @@ void adam_copy_update(torch::Tensor data, torch::Tensor m, torch::Tensor v,
              wire_bit(out, "out", n, kWireOut);
   mv_launch_adam(f32(data), f32(m), f32(v), delta.data_ptr(), out.data_ptr(),
                  wire, b1, b2, step, rbc2, decay, eps, n, cur_stream());
+}
+
+// 1-bit Add wire (onebit_filter.py): 136 bytes per block of 1024 elements
+int64_t onebit_bytes(int64_t n) { return 136 * ((n + 1023) / 1024); }
+
+void check_payload(const torch::Tensor& t, const char* name, int64_t bytes) {
+  check_dev(t, name, torch::kUInt8);
+  TORCH_CHECK(t.numel() == bytes, name, " must hold ", bytes, " bytes");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 8 == 0, name,
+              " must be 8-byte aligned");
+}
+
+// payload <- code of (residual + delta); residual <- the quantisation error.
+// delta and residual may be 4-byte-aligned views (pieces of a table).
+void onebit_encode(torch::Tensor delta, torch::Tensor residual,
+                   torch::Tensor payload) {
+  int64_t n = check_same({{"delta", delta}, {"residual", residual}});
+  TORCH_CHECK(n >= 1, "onebit_encode: empty piece");
+  TORCH_CHECK((n + 1023) / 1024 <= INT32_MAX, "onebit_encode: piece too large");
+  check_payload(payload, "payload", onebit_bytes(n));
+  mv_launch_onebit_encode(f32(delta), f32(residual),
+                          payload.data_ptr<uint8_t>(), n, cur_stream());
+}
+
+// out <- the sum, in payload order, of the values nparts consecutive
+// payloads of one n-element piece decode to
+void onebit_decode_sum(torch::Tensor out, torch::Tensor payloads,
+                       int64_t nparts) {
+  check_f32(out, "out");
+  int64_t n = out.numel();
+  TORCH_CHECK(n >= 1, "onebit_decode_sum: empty piece");
+  TORCH_CHECK(nparts >= 1 && nparts <= INT32_MAX,
+              "onebit_decode_sum: nparts must be >= 1");
+  check_payload(payloads, "payloads", nparts * onebit_bytes(n));
+  mv_launch_onebit_decode_sum(f32(out), payloads.data_ptr<uint8_t>(),
+                              (int)nparts, n, cur_stream());
 }
 
 void row_gather_out(torch::Tensor out, torch::Tensor shard, torch::Tensor rows) {
@@ -753,6 +793,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("data"), py::arg("m"), py::arg("v"), py::arg("delta"),
         py::arg("out"), py::arg("b1"), py::arg("b2"), py::arg("step"),
         py::arg("rbc2"), py::arg("decay"), py::arg("eps"));
+  m.def("onebit_encode", &onebit_encode,
+        "1-bit wire: payload = code(residual + delta), residual = the error",
+        py::arg("delta"), py::arg("residual"), py::arg("payload"));
+  m.def("onebit_decode_sum", &onebit_decode_sum,
+        "1-bit wire: out = sum over nparts payloads of their decoded values",
+        py::arg("out"), py::arg("payloads"), py::arg("nparts"));
   m.def("row_gather", &row_gather,
         "K6: out[i] = shard[rows[i]]; dtype=torch.bfloat16 narrows",
         py::arg("shard"), py::arg("rows"), py::arg("dtype") = py::none());

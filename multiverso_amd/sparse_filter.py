@@ -3,8 +3,9 @@
 Capability parity with the reference SparseFilter<data,index>
 (include/multiverso/util/quantization_util.h:25-158): per-payload, if more
 than half the values are zero, encode as (index, value) pairs with a size
-header; otherwise pass through dense. ``OneBitsFilter`` is an empty stub
-in the reference (:160-161) and is intentionally not reproduced.
+header; otherwise pass through dense. ``OneBitsFilter``, an empty class in
+the reference (:160-161), lives in onebit_filter.py: 1-bit quantisation with
+error feedback for whole-table Add (``add_filter="onebit"``).
 
 MI355X placement: dense whole-table traffic goes
 through reduce-scatter/all-gather and is never filtered (collectives need

@@ -15,6 +15,11 @@ the owned shard. Both can be issued async and overlap with compute.
 delta is rounded to bf16 once and travels so, the owner's updater kernel
 widens it in registers, and Get returns the fp32 shard rounded to bf16. The
 shard, updater state and Store/Load stay fp32.
+
+``add_filter="onebit"`` (float32 tables) sends every whole-table Add through
+onebit_filter: signs plus two scales per 1024 elements, the quantisation
+error kept in ``self.residual`` (fp32, the full table size, per worker) and
+added to the next delta. Get, Store and Load are unfiltered.
 """
 
 from __future__ import annotations
@@ -23,7 +28,8 @@ from typing import Optional
 
 import torch
 
-from ..comm import Handle, ShardSpec, allgather_shards, reduce_scatter_delta
+from ..comm import (Handle, ShardSpec, allgather_shards,
+                    onebit_exchange_delta, reduce_scatter_delta)
 from ..dashboard import monitor
 from ..log import CHECK
 from ..updaters import AddOption
@@ -33,9 +39,11 @@ from .base import Table
 class ArrayTable(Table):
     def __init__(self, size: int, dtype: torch.dtype = torch.float32,
                  updater_type: Optional[str] = None,
-                 wire_dtype: Optional[torch.dtype] = None) -> None:
+                 wire_dtype: Optional[torch.dtype] = None,
+                 add_filter: Optional[str] = None) -> None:
         super().__init__(updater_type)
         self._set_wire(wire_dtype, dtype)
+        self._set_add_filter(add_filter, dtype, wire_dtype)
         CHECK(size >= self.zoo.num_servers,
               f"table size {size} must be >= num_servers "
               f"{self.zoo.num_servers} (reference array_table.cpp:14)")
@@ -156,13 +164,22 @@ class ArrayTable(Table):
                 return self._track(h)
             h.wait()
             return h
+        if self.add_filter and self.zoo.size == 1:
+            # the decoded tensor is the table's own: the caller may mutate
+            # its delta at once
+            delta = self._filter_local(delta)
         if self.zoo.size == 1 and self.shard.is_cuda:
             self.flush()                 # at most one deferred Add
             self._deferred = (delta, option, delta._version)
             return Handle()
         with monitor("worker.add"):
-            chunk, h = reduce_scatter_delta(delta, self.spec, 1,
-                                            async_op=async_op)
+            if self.add_filter and self.zoo.size > 1:
+                chunk, h = onebit_exchange_delta(
+                    delta, self._filter_residual(delta.numel()), self.spec,
+                    1, async_op=async_op)
+            else:
+                chunk, h = reduce_scatter_delta(delta, self.spec, 1,
+                                                async_op=async_op)
             if async_op:
                 upd, opt = self.updater, option
 

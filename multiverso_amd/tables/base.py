@@ -51,6 +51,10 @@ class Table:
         # dtype of Add/Get payloads; tables that take ``wire_dtype`` set it
         # (_set_wire), None means the shard's own dtype
         self.wire: Optional[torch.dtype] = None
+        # whole-table Add filter; tables that take ``add_filter`` set it
+        # (_set_add_filter)
+        self.add_filter: Optional[str] = None
+        self.residual: Optional[torch.Tensor] = None
         # async mode: a fast worker's request can arrive before THIS
         # rank finished constructing the table (the reference's
         # RegisterTable round-trip subsumed this); the server thread
@@ -85,6 +89,48 @@ class Table:
             raise TypeError(f"wire_dtype {wire_dtype} is not supported on a "
                             f"{dtype} table (torch.bfloat16 needs a float32 "
                             f"table; None keeps the table's dtype)")
+
+    def _set_add_filter(self, add_filter: Optional[str], dtype: torch.dtype,
+                        wire_dtype: Optional[torch.dtype]) -> None:
+        """Resolve the ``add_filter`` keyword: None sends whole-table deltas
+        as they are; "onebit" sends them through onebit_filter (1 bit per
+        element plus two fp32 scales per 1024, error feedback), on both
+        planes and on a single rank alike. float32 tables only.
+
+        ``self.residual`` is the error-feedback state: fp32, the table's
+        FULL flat size (not this rank's shard: a worker quantises the whole
+        delta it sends), on the table's device, zero at the first filtered
+        Add, where it is allocated. It costs 4 bytes per element per worker.
+        Like updater state it is not written by ``store`` or checkpoints."""
+        self.add_filter = add_filter
+        self.residual: Optional[torch.Tensor] = None
+        if add_filter is None:
+            return
+        if add_filter != "onebit":
+            raise ValueError(f"add_filter {add_filter!r} is not known "
+                             f"(None or 'onebit')")
+        if dtype != torch.float32:
+            raise TypeError(f"add_filter='onebit' needs a float32 table, "
+                            f"not {dtype}")
+        if wire_dtype == torch.bfloat16:
+            raise TypeError("add_filter='onebit' together with "
+                            "wire_dtype=torch.bfloat16 is not supported yet "
+                            "(a follow-up: bf16 Get under a 1-bit Add)")
+
+    def _filter_residual(self, numel: int) -> torch.Tensor:
+        if self.residual is None:
+            self.residual = torch.zeros(numel, dtype=torch.float32,
+                                        device=self.device)
+        return self.residual
+
+    def _filter_local(self, delta: torch.Tensor) -> torch.Tensor:
+        """Single rank: what the owner would decode from this delta, as a
+        fresh fp32 tensor of the table's own (the semantics do not depend on
+        the world size, as the bf16 wire still rounds on one rank)."""
+        from .. import onebit_filter
+        payload = onebit_filter.encode(
+            delta, self._filter_residual(delta.numel()))
+        return onebit_filter.decode_sum(payload, delta.numel(), 1)
 
     def _stage_get(self, out: torch.Tensor) -> bool:
         """bf16 wire only: a Get buffer of another dtype (fp32, say) is

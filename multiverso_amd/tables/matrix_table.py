@@ -27,6 +27,12 @@ MI355X mapping:
   kernels widen and narrow in registers; duplicate rows of a keyed Add are
   summed in fp32 after widening.
 
+- ``add_filter="onebit"`` (float32 tables): every whole-table Add goes
+  through onebit_filter — signs plus two scales per 1024 elements, the
+  quantisation error kept in ``self.residual`` (fp32, the full table size,
+  per worker) and added to the next delta. Row-keyed ops, Get, Store and
+  Load are unfiltered and leave the residual alone.
+
 Sparse/stale-aware Get (SparseMatrixTable's per-(worker,row) freshness
 bitmap) is implemented in sparse_matrix.py on top of this class; it takes no
 ``wire_dtype``.
@@ -39,7 +45,8 @@ from typing import Optional, Tuple
 import torch
 
 from ..comm import (Handle, ShardSpec, all_to_all_rows, all_to_all_values,
-                    allgather_shards, reduce_scatter_delta)
+                    allgather_shards, onebit_exchange_delta,
+                    reduce_scatter_delta)
 from ..dashboard import monitor
 from ..log import CHECK
 from ..updaters import AddOption
@@ -51,9 +58,11 @@ class MatrixTable(Table):
                  dtype: torch.dtype = torch.float32,
                  updater_type: Optional[str] = None,
                  random_init: Optional[Tuple[float, float]] = None,
-                 wire_dtype: Optional[torch.dtype] = None) -> None:
+                 wire_dtype: Optional[torch.dtype] = None,
+                 add_filter: Optional[str] = None) -> None:
         super().__init__(updater_type)
         self._set_wire(wire_dtype, dtype)
+        self._set_add_filter(add_filter, dtype, wire_dtype)
         CHECK(num_row >= self.zoo.num_servers,
               f"num_row {num_row} must be >= num_servers")
         self.num_row = num_row
@@ -198,13 +207,22 @@ class MatrixTable(Table):
                 return self._track(h)
             h.wait()
             return h
+        if self.add_filter and self.zoo.size == 1:
+            # the decoded tensor is the table's own: the caller may mutate
+            # its delta at once
+            delta = self._filter_local(delta)
         if self.zoo.size == 1 and self.shard.is_cuda:
             self.flush()                 # at most one deferred Add
             self._deferred = (delta, option, delta._version)
             return Handle()
         with monitor("worker.add"):
-            chunk, h = reduce_scatter_delta(delta, self.spec, self.num_col,
-                                            async_op=async_op)
+            if self.add_filter and self.zoo.size > 1:
+                chunk, h = onebit_exchange_delta(
+                    delta, self._filter_residual(delta.numel()), self.spec,
+                    self.num_col, async_op=async_op)
+            else:
+                chunk, h = reduce_scatter_delta(delta, self.spec, self.num_col,
+                                                async_op=async_op)
             if async_op:
                 upd, opt = self.updater, option
 
