@@ -12,36 +12,38 @@
 extern "C" {
 // elementwise updaters: a non-null `out` (the pointer before `wire`)
 // selects the fused Add+Get form. The fp32 forms take the delta and `out`
-// as void* and, in `wire`, the WIRE_* bits that say which holds bf16.
+// as void* and, in `wire`, the WIRE_* bits that say which holds bf16. The
+// trailing int of the updaters is the sweep direction (1 = descending): a
+// performance hint, the result is the same either way.
 void mv_launch_copy(void*, const float*, int, int64_t, hipStream_t);
-void mv_launch_add(float*, const void*, int, int64_t, hipStream_t);
-void mv_launch_add_f64(double*, const double*, int64_t, hipStream_t);
-void mv_launch_add_i32(int32_t*, const int32_t*, int64_t, hipStream_t);
-void mv_launch_add_i64(int64_t*, const int64_t*, int64_t, hipStream_t);
+void mv_launch_add(float*, const void*, int, int64_t, hipStream_t, int);
+void mv_launch_add_f64(double*, const double*, int64_t, hipStream_t, int);
+void mv_launch_add_i32(int32_t*, const int32_t*, int64_t, hipStream_t, int);
+void mv_launch_add_i64(int64_t*, const int64_t*, int64_t, hipStream_t, int);
 void mv_launch_sgd(float*, const void*, void*, int, float, int64_t,
-                   hipStream_t);
+                   hipStream_t, int);
 void mv_launch_sgd_f64(double*, const double*, double*, double, int64_t,
-                       hipStream_t);
+                       hipStream_t, int);
 void mv_launch_momentum(float*, float*, const void*, void*, int, float,
-                        int64_t, hipStream_t);
+                        int64_t, hipStream_t, int);
 void mv_launch_momentum_f64(double*, double*, const double*, double, int64_t,
-                            hipStream_t);
+                            hipStream_t, int);
 void mv_launch_adagrad(float*, float*, const void*, void*, int, float, float,
-                       float, int64_t, hipStream_t);
+                       float, int64_t, hipStream_t, int);
 void mv_launch_adagrad_f64(double*, double*, const double*, double, double,
-                           double, int64_t, hipStream_t);
+                           double, int64_t, hipStream_t, int);
 void mv_launch_dcasgd(float*, float*, const void*, void*, int, float, float,
-                      int64_t, hipStream_t);
+                      int64_t, hipStream_t, int);
 void mv_launch_dcasgda(float*, float*, float*, const void*, void*, int, float,
-                       float, float, float, int64_t, hipStream_t);
+                       float, float, float, int64_t, hipStream_t, int);
 // adam: (..., b1, b2, step = lr/(1-b1^t), rbc2 = 1/sqrt(1-b2^t),
 // decay = 1-lr*wd, eps, n), all scalars in double
 void mv_launch_adam(float*, float*, float*, const void*, void*, int, double,
                     double, double, double, double, double, int64_t,
-                    hipStream_t);
+                    hipStream_t, int);
 void mv_launch_adam_f64(double*, double*, double*, const double*, double,
                         double, double, double, double, double, int64_t,
-                        hipStream_t);
+                        hipStream_t, int);
 // keyed kernels: `vals` (the gather's `out`) is void* followed by `wire`
 void mv_launch_onebit_encode(const float*, float*, uint8_t*, int64_t,
                              hipStream_t);
@@ -170,22 +172,22 @@ void nt_copy(torch::Tensor dst, torch::Tensor src) {
   mv_launch_copy(dst.data_ptr(), f32(src), wire, n, cur_stream());
 }
 
-void add_inplace(torch::Tensor data, torch::Tensor delta) {
+void add_inplace(torch::Tensor data, torch::Tensor delta, bool reverse) {
   // dtype-dispatched K1 (reference instantiates int/float/double tables,
   // array_table.cpp:153-154; int updater is add-only, updater.cpp:40-43)
   auto st = data.scalar_type();
   int64_t n = check_same({{"data", data}}, st);
   int wire = wire_bit(delta, "delta", n, kWireDelta, st);
   if (st == torch::kFloat32)
-    mv_launch_add(f32(data), delta.data_ptr(), wire, n, cur_stream());
+    mv_launch_add(f32(data), delta.data_ptr(), wire, n, cur_stream(), reverse);
   else if (st == torch::kFloat64)
-    mv_launch_add_f64(f64(data), f64(delta), n, cur_stream());
+    mv_launch_add_f64(f64(data), f64(delta), n, cur_stream(), reverse);
   else if (st == torch::kInt32)
     mv_launch_add_i32(data.data_ptr<int32_t>(), delta.data_ptr<int32_t>(), n,
-                      cur_stream());
+                      cur_stream(), reverse);
   else if (st == torch::kInt64)
     mv_launch_add_i64(data.data_ptr<int64_t>(), delta.data_ptr<int64_t>(), n,
-                      cur_stream());
+                      cur_stream(), reverse);
   else
     TORCH_CHECK(false, "add_inplace: unsupported dtype ", data.dtype());
 }
@@ -193,133 +195,136 @@ void add_inplace(torch::Tensor data, torch::Tensor delta) {
 // data += sign * delta; `out`, when given, also receives the updated data
 void launch_sgd(const char* fn, const torch::Tensor& data,
                 const torch::Tensor& delta, const torch::Tensor* out,
-                double sign) {
+                double sign, bool reverse) {
   auto st = data.scalar_type();
   int64_t n = check_same({{"data", data}}, st);
   int wire = wire_bit(delta, "delta", n, kWireDelta, st);
   if (out) wire |= wire_bit(*out, "out", n, kWireOut, st);
   if (st == torch::kFloat32)
     mv_launch_sgd(f32(data), delta.data_ptr(), out ? out->data_ptr() : nullptr,
-                  wire, (float)sign, n, cur_stream());
+                  wire, (float)sign, n, cur_stream(), reverse);
   else if (st == torch::kFloat64)
     mv_launch_sgd_f64(f64(data), f64(delta), out ? f64(*out) : nullptr, sign,
-                      n, cur_stream());
+                      n, cur_stream(), reverse);
   else
     TORCH_CHECK(false, fn, ": unsupported dtype ", data.dtype());
 }
 
-void sgd_update(torch::Tensor data, torch::Tensor delta) {
-  launch_sgd("sgd_update", data, delta, nullptr, -1.0);
+void sgd_update(torch::Tensor data, torch::Tensor delta, bool reverse) {
+  launch_sgd("sgd_update", data, delta, nullptr, -1.0, reverse);
 }
 
 void sgd_copy_update(torch::Tensor data, torch::Tensor delta,
-                     torch::Tensor out, double sign) {
-  launch_sgd("sgd_copy_update", data, delta, &out, sign);
+                     torch::Tensor out, double sign, bool reverse) {
+  launch_sgd("sgd_copy_update", data, delta, &out, sign, reverse);
 }
 
 void momentum_update(torch::Tensor data, torch::Tensor m, torch::Tensor delta,
-                     double mu) {
+                     double mu, bool reverse) {
   auto st = data.scalar_type();
   int64_t n = check_same({{"data", data}, {"m", m}}, st);
   int wire = wire_bit(delta, "delta", n, kWireDelta, st);
   if (st == torch::kFloat32)
     mv_launch_momentum(f32(data), f32(m), delta.data_ptr(), nullptr, wire,
-                       (float)mu, n, cur_stream());
+                       (float)mu, n, cur_stream(), reverse);
   else if (st == torch::kFloat64)
     mv_launch_momentum_f64(f64(data), f64(m), f64(delta), mu, n,
-                           cur_stream());
+                           cur_stream(), reverse);
   else
     TORCH_CHECK(false, "momentum_update: unsupported dtype ", data.dtype());
 }
 
 void momentum_copy_update(torch::Tensor data, torch::Tensor m,
-                          torch::Tensor delta, torch::Tensor out, double mu) {
+                          torch::Tensor delta, torch::Tensor out, double mu,
+                          bool reverse) {
   int64_t n = check_same({{"data", data}, {"m", m}});
   int wire = wire_bit(delta, "delta", n, kWireDelta) |
              wire_bit(out, "out", n, kWireOut);
   mv_launch_momentum(f32(data), f32(m), delta.data_ptr(), out.data_ptr(),
-                     wire, (float)mu, n, cur_stream());
+                     wire, (float)mu, n, cur_stream(), reverse);
 }
 
 void adagrad_update(torch::Tensor data, torch::Tensor gsq, torch::Tensor delta,
-                    double lr, double rho, double eps) {
+                    double lr, double rho, double eps, bool reverse) {
   auto st = data.scalar_type();
   int64_t n = check_same({{"data", data}, {"gsq", gsq}}, st);
   int wire = wire_bit(delta, "delta", n, kWireDelta, st);
   if (st == torch::kFloat32)
     mv_launch_adagrad(f32(data), f32(gsq), delta.data_ptr(), nullptr, wire,
-                      (float)lr, (float)rho, (float)eps, n, cur_stream());
+                      (float)lr, (float)rho, (float)eps, n, cur_stream(),
+                      reverse);
   else if (st == torch::kFloat64)
     mv_launch_adagrad_f64(f64(data), f64(gsq), f64(delta), lr, rho, eps, n,
-                          cur_stream());
+                          cur_stream(), reverse);
   else
     TORCH_CHECK(false, "adagrad_update: unsupported dtype ", data.dtype());
 }
 
 void adagrad_copy_update(torch::Tensor data, torch::Tensor gsq,
                          torch::Tensor delta, torch::Tensor out,
-                         double lr, double rho, double eps) {
+                         double lr, double rho, double eps, bool reverse) {
   int64_t n = check_same({{"data", data}, {"gsq", gsq}});
   int wire = wire_bit(delta, "delta", n, kWireDelta) |
              wire_bit(out, "out", n, kWireOut);
   mv_launch_adagrad(f32(data), f32(gsq), delta.data_ptr(), out.data_ptr(),
-                    wire, (float)lr, (float)rho, (float)eps, n, cur_stream());
+                    wire, (float)lr, (float)rho, (float)eps, n, cur_stream(),
+                    reverse);
 }
 
 void dcasgd_update(torch::Tensor data, torch::Tensor bak, torch::Tensor delta,
-                   double lr, double lambda) {
+                   double lr, double lambda, bool reverse) {
   int64_t n = check_same({{"data", data}, {"bak", bak}});
   int wire = wire_bit(delta, "delta", n, kWireDelta);
   mv_launch_dcasgd(f32(data), f32(bak), delta.data_ptr(), nullptr, wire,
-                   (float)lr, (float)lambda, n, cur_stream());
+                   (float)lr, (float)lambda, n, cur_stream(), reverse);
 }
 
 void dcasgd_copy_update(torch::Tensor data, torch::Tensor bak,
                         torch::Tensor delta, torch::Tensor out,
-                        double lr, double lambda) {
+                        double lr, double lambda, bool reverse) {
   int64_t n = check_same({{"data", data}, {"bak", bak}});
   int wire = wire_bit(delta, "delta", n, kWireDelta) |
              wire_bit(out, "out", n, kWireOut);
   mv_launch_dcasgd(f32(data), f32(bak), delta.data_ptr(), out.data_ptr(),
-                   wire, (float)lr, (float)lambda, n, cur_stream());
+                   wire, (float)lr, (float)lambda, n, cur_stream(), reverse);
 }
 
 void dcasgda_update(torch::Tensor data, torch::Tensor bak, torch::Tensor msq,
                     torch::Tensor delta, double lr, double lambda, double rho,
-                    double eps) {
+                    double eps, bool reverse) {
   int64_t n = check_same({{"data", data}, {"bak", bak}, {"msq", msq}});
   int wire = wire_bit(delta, "delta", n, kWireDelta);
   mv_launch_dcasgda(f32(data), f32(bak), f32(msq), delta.data_ptr(), nullptr,
                     wire, (float)lr, (float)lambda, (float)rho, (float)eps, n,
-                    cur_stream());
+                    cur_stream(), reverse);
 }
 
 void dcasgda_copy_update(torch::Tensor data, torch::Tensor bak,
                          torch::Tensor msq, torch::Tensor delta,
                          torch::Tensor out, double lr, double lambda,
-                         double rho, double eps) {
+                         double rho, double eps, bool reverse) {
   int64_t n = check_same({{"data", data}, {"bak", bak}, {"msq", msq}});
   int wire = wire_bit(delta, "delta", n, kWireDelta) |
              wire_bit(out, "out", n, kWireOut);
   mv_launch_dcasgda(f32(data), f32(bak), f32(msq), delta.data_ptr(),
                     out.data_ptr(), wire, (float)lr, (float)lambda,
-                    (float)rho, (float)eps, n, cur_stream());
+                    (float)rho, (float)eps, n, cur_stream(), reverse);
 }
 
 // step = lr / (1 - b1^t), rbc2 = 1 / sqrt(1 - b2^t), decay = 1 - lr*wd:
 // the caller owns the update count t
 void adam_update(torch::Tensor data, torch::Tensor m, torch::Tensor v,
                  torch::Tensor delta, double b1, double b2, double step,
-                 double rbc2, double decay, double eps) {
+                 double rbc2, double decay, double eps, bool reverse) {
   auto st = data.scalar_type();
   int64_t n = check_same({{"data", data}, {"m", m}, {"v", v}}, st);
   int wire = wire_bit(delta, "delta", n, kWireDelta, st);
   if (st == torch::kFloat32)
     mv_launch_adam(f32(data), f32(m), f32(v), delta.data_ptr(), nullptr, wire,
-                   b1, b2, step, rbc2, decay, eps, n, cur_stream());
+                   b1, b2, step, rbc2, decay, eps, n, cur_stream(), reverse);
   else if (st == torch::kFloat64)
     mv_launch_adam_f64(f64(data), f64(m), f64(v), f64(delta), b1, b2, step,
-                       rbc2, decay, eps, n, cur_stream());
+                       rbc2, decay, eps, n, cur_stream(), reverse);
   else
     TORCH_CHECK(false, "adam_update: unsupported dtype ", data.dtype());
 }
@@ -327,12 +332,13 @@ void adam_update(torch::Tensor data, torch::Tensor m, torch::Tensor v,
 void adam_copy_update(torch::Tensor data, torch::Tensor m, torch::Tensor v,
                       torch::Tensor delta, torch::Tensor out, double b1,
                       double b2, double step, double rbc2, double decay,
-                      double eps) {
+                      double eps, bool reverse) {
   int64_t n = check_same({{"data", data}, {"m", m}, {"v", v}});
   int wire = wire_bit(delta, "delta", n, kWireDelta) |
              wire_bit(out, "out", n, kWireOut);
   mv_launch_adam(f32(data), f32(m), f32(v), delta.data_ptr(), out.data_ptr(),
-                 wire, b1, b2, step, rbc2, decay, eps, n, cur_stream());
+                 wire, b1, b2, step, rbc2, decay, eps, n, cur_stream(),
+                 reverse);
 }
 
 // 1-bit Add wire (onebit_filter.py): 136 bytes per block of 1024 elements
@@ -762,37 +768,55 @@ void lr_ftrl_scatter(torch::Tensor zn, torch::Tensor keys,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // fp32 shards also take a bf16 delta / vals / out (the bf16 wire format)
-  m.def("add_inplace", &add_inplace, "K1: data += delta (fp32, fused)");
+  // The whole-shard updaters take a trailing reverse=False: True sweeps
+  // the arrays from the top down. It is a performance hint (alternate it
+  // from pass to pass and the Infinity Cache serves the turning end); the
+  // result is bit for bit the same either way.
+  auto rev = py::arg("reverse") = false;
+  auto data = py::arg("data"), delta = py::arg("delta"), out = py::arg("out");
+  m.def("add_inplace", &add_inplace, "K1: data += delta (fp32, fused)", data,
+        delta, rev);
   m.def("nt_copy", &nt_copy,
         "K7: non-temporal streaming copy (a bf16 dst narrows)");
-  m.def("sgd_update", &sgd_update, "K2: data -= delta");
-  m.def("momentum_update", &momentum_update, "K3: fused momentum update");
-  m.def("adagrad_update", &adagrad_update, "K4: fused adagrad update");
+  m.def("sgd_update", &sgd_update, "K2: data -= delta", data, delta, rev);
+  m.def("momentum_update", &momentum_update, "K3: fused momentum update",
+        data, py::arg("m"), delta, py::arg("mu"), rev);
+  m.def("adagrad_update", &adagrad_update, "K4: fused adagrad update", data,
+        py::arg("gsq"), delta, py::arg("lr"), py::arg("rho"), py::arg("eps"),
+        rev);
   m.def("momentum_copy_update", &momentum_copy_update,
-        "fused momentum Add+Get");
+        "fused momentum Add+Get", data, py::arg("m"), delta, out,
+        py::arg("mu"), rev);
   m.def("adagrad_copy_update", &adagrad_copy_update,
-        "fused adagrad Add+Get");
+        "fused adagrad Add+Get", data, py::arg("gsq"), delta, out,
+        py::arg("lr"), py::arg("rho"), py::arg("eps"), rev);
   m.def("dcasgd_copy_update", &dcasgd_copy_update,
-        "fused dcasgd Add+Get");
+        "fused dcasgd Add+Get", data, py::arg("bak"), delta, out,
+        py::arg("lr"), py::arg("lambda_"), rev);
   m.def("dcasgda_copy_update", &dcasgda_copy_update,
-        "fused dcasgda Add+Get");
+        "fused dcasgda Add+Get", data, py::arg("bak"), py::arg("msq"), delta,
+        out, py::arg("lr"), py::arg("lambda_"), py::arg("rho"),
+        py::arg("eps"), rev);
   m.def("sgd_copy_update", &sgd_copy_update,
         "fused Add+Get: data (+/-)= delta; out = data (saves the Get's "
-        "shard re-read at N=1)");
+        "shard re-read at N=1)", data, delta, out, py::arg("sign"), rev);
   m.def("dcasgd_update", &dcasgd_update,
-        "DC-ASGD: delay-compensated update with per-worker backup");
+        "DC-ASGD: delay-compensated update with per-worker backup", data,
+        py::arg("bak"), delta, py::arg("lr"), py::arg("lambda_"), rev);
   m.def("dcasgda_update", &dcasgda_update,
-        "DC-ASGD-a: adaptive lambda via mean-square of gradients");
+        "DC-ASGD-a: adaptive lambda via mean-square of gradients", data,
+        py::arg("bak"), py::arg("msq"), delta, py::arg("lr"),
+        py::arg("lambda_"), py::arg("rho"), py::arg("eps"), rev);
   m.def("adam_update", &adam_update,
         "fused Adam/AdamW step (fp32, fp64); step = lr/(1-b1^t), "
         "rbc2 = 1/sqrt(1-b2^t), decay = 1-lr*wd",
         py::arg("data"), py::arg("m"), py::arg("v"), py::arg("delta"),
         py::arg("b1"), py::arg("b2"), py::arg("step"), py::arg("rbc2"),
-        py::arg("decay"), py::arg("eps"));
+        py::arg("decay"), py::arg("eps"), rev);
   m.def("adam_copy_update", &adam_copy_update, "fused adam Add+Get",
         py::arg("data"), py::arg("m"), py::arg("v"), py::arg("delta"),
         py::arg("out"), py::arg("b1"), py::arg("b2"), py::arg("step"),
-        py::arg("rbc2"), py::arg("decay"), py::arg("eps"));
+        py::arg("rbc2"), py::arg("decay"), py::arg("eps"), rev);
   m.def("onebit_encode", &onebit_encode,
         "1-bit wire: payload = code(residual + delta), residual = the error",
         py::arg("delta"), py::arg("residual"), py::arg("payload"));

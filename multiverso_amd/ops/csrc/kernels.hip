@@ -10,14 +10,15 @@
 // the shape is {block = 256 threads (4 waves of 64), float4 16B/lane
 // vectorized loads/stores, grid-stride}. The grid cap is probe-swept per
 // stream count (defines below): UPD_GRID = 768 blocks for add/sgd,
-// STATE_GRID = 768 for the stateful updaters, ELEM_GRID = 1024 for the
-// plain copy and the f64/int forms, COPY_BLOCK = 1024 threads x
-// COPY_GRID = 768 blocks for the fused Add+Get bodies; MAX_GRID = 2048
-// (256 CUs x 8 blocks) only caps the row-keyed, word2vec and logreg
-// kernels. The stateful updaters (momentum/adagrad/dcasgd/adam) fuse the
-// state read-modify-write into the same pass as the weight update — one trip
-// through HBM3E instead of the 3-4 separate passes a torch-op composition
-// would make.
+// STATE_GRID = 768 for the stateful updaters, both with or without the
+// fused Get buffer, ELEM_GRID = 1024 for the plain copy and the f64/int
+// forms; MAX_GRID = 2048 (256 CUs x 8 blocks) only caps the row-keyed,
+// word2vec and logreg kernels. Whole-shard passes alternate their sweep
+// direction so that the Infinity Cache serves the turning end (SWEEP note
+// at launch_elem). The stateful updaters (momentum/adagrad/dcasgd/adam) fuse
+// the state read-modify-write into the same pass as the weight update — one
+// trip through HBM3E instead of the 3-4 separate passes a torch-op
+// composition would make.
 //
 // No CUDA compatibility paths: this file is HIP-only, compiled by hipcc
 // with --offload-arch=gfx950.
@@ -43,12 +44,22 @@
 // (tools/probe_sgd2.hip round-2 sweep). The pure 2-stream copy keeps
 // ELEM_GRID (6.15 at 1024).
 #define UPD_GRID 768
-// 4-stream fused Add+Get kernels prefer FAT blocks: 1024 threads x 768+
-// blocks measured 6.14 TB/s vs 5.87 at 256x768 (tools/probe_sgd2.hip
-// round-2 sweep; the 2/3-stream kernels regress at 1024 — they keep
-// BLOCK=256). Grid counts are in BLOCKS of COPY_BLOCK threads.
+// The fused Add+Get bodies ran FAT blocks (COPY_BLOCK = 1024 threads x 768)
+// while every pass swept forward: 6.14 TB/s vs 5.87 at 256x768 on the
+// round-2 box (tools/probe_sgd2.hip). Under the alternating sweep they do
+// not (tools/probe_sweep_dir.hip, range over its runs, ms per 2.0 GB
+// pass, delta never reused): a CU holds 32 waves, so only 512 of 768
+// 16-wave blocks are resident at once, the other 256 start late at the far
+// end and break the front the next pass turns on; 1024x768 alternating
+// 0.343-0.358 (forward, all non-temporal, as before: 0.361-0.377), and at
+// 1024x512, all resident, 0.323-0.331. 256x768 (3 blocks of 4 waves per CU,
+// all resident) 0.292-0.298 and 256x512 0.289-0.295; 256x384, x640, x1024
+// and x2048 are slower (0.307-0.333). The fused bodies therefore use BLOCK
+// threads and their updater's own cap, chosen for residency; 768 over 512
+// because the 3-stream body is level between them and the 6-stream body
+// was measured with the shard-only policy at 768 (0.498 vs 0.571 forward).
+// COPY_BLOCK stays the block of k_lr_dense_fwd.
 #define COPY_BLOCK 1024
-#define COPY_GRID 768
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -84,6 +95,20 @@ static __device__ __forceinline__ V ld(const T* p, int64_t i) {
 template <class V, class T>
 static __device__ __forceinline__ void st(T* p, int64_t i, V v) {
   ntstore((V*)p + i, v);
+}
+
+// The shard's own load in a whole-shard pass (KEEP) is a plain, cacheable
+// one; everything else such a pass touches stays non-temporal. Consecutive
+// passes run in opposite directions (k_elem's `rev`), and only a plainly
+// loaded line is still served by the Infinity Cache when the next pass
+// comes back to it; a non-temporal load never hits, and the state, delta
+// and Get-buffer streams kept non-temporal leave the cache to the shard
+// (tools/probe_sweep_dir.hip, profiles/sweep_direction.md). The row-keyed
+// kernels keep the non-temporal form (KEEP = false).
+template <class V, bool KEEP, class T>
+static __device__ __forceinline__ V ld_shard(const T* p, int64_t i) {
+  if constexpr (KEEP) return *((const V*)p + i);
+  else return ld<V>(p, i);
 }
 
 // bf16 wire format: the delta / vals a kernel reads and the Get buffer it
@@ -197,7 +222,7 @@ struct AddOp {
   using elem = T;
   T* data; const D* delta;
   template <class V> __device__ __forceinline__ V step(int64_t i) const {
-    V v = ld<V>(data, i) + ld<V>(delta, i);
+    V v = ld_shard<V, true>(data, i) + ld<V>(delta, i);
     st(data, i, v);
     return v;
   }
@@ -210,7 +235,7 @@ struct SgdOp {
   using elem = T;
   T* data; const D* delta; T sign;
   template <class V> __device__ __forceinline__ V step(int64_t i) const {
-    V v = ld<V>(data, i) + sign * ld<V>(delta, i);
+    V v = ld_shard<V, true>(data, i) + sign * ld<V>(delta, i);
     st(data, i, v);
     return v;
   }
@@ -220,9 +245,9 @@ template <class T, class D = T>
 struct MomentumOp {
   using elem = T;
   T* data; T* m; const D* delta; T mu;
-  template <class V> __device__ __forceinline__ V step_at(int64_t i,
-                                                          V g) const {
-    V d = ld<V>(data, i);
+  template <class V, bool KEEP = false>
+  __device__ __forceinline__ V step_at(int64_t i, V g) const {
+    V d = ld_shard<V, KEEP>(data, i);
     // explicit fma, so that every instantiation rounds alike: left to
     // contract on its own, the compiler fused mu*m + (1-mu)*delta in the
     // float4 bodies and the fused tail but not in the plain scalar tail
@@ -233,7 +258,7 @@ struct MomentumOp {
     return d;
   }
   template <class V> __device__ __forceinline__ V step(int64_t i) const {
-    return step_at<V>(i, ld<V>(delta, i));
+    return step_at<V, true>(i, ld<V>(delta, i));
   }
 };
 
@@ -242,7 +267,7 @@ struct AdagradOp {
   using elem = T;
   T* data; T* gsq; const D* delta; T inv_lr, rho, eps;
   template <class V> __device__ __forceinline__ V step(int64_t i) const {
-    V d = ld<V>(data, i), G = ld<V>(gsq, i);
+    V d = ld_shard<V, true>(data, i), G = ld<V>(gsq, i);
     V g = ld<V>(delta, i) * inv_lr;
     G += g * g;
     // double keeps the exact divide; fp32 uses the hardware rsq
@@ -269,16 +294,16 @@ template <class D = float>
 struct DcasgdOp {
   using elem = float;
   float* data; float* bak; const D* delta; float lr, lambda;
-  template <class V> __device__ __forceinline__ V step_at(int64_t i,
-                                                          V g) const {
-    V w = ld<V>(data, i), b = ld<V>(bak, i);
+  template <class V, bool KEEP = false>
+  __device__ __forceinline__ V step_at(int64_t i, V g) const {
+    V w = ld_shard<V, KEEP>(data, i), b = ld<V>(bak, i);
     w -= lr * (g + lambda * g * g * (w - b));
     st(data, i, w);
     st(bak, i, w);
     return w;
   }
   template <class V> __device__ __forceinline__ V step(int64_t i) const {
-    return step_at<V>(i, ld<V>(delta, i));
+    return step_at<V, true>(i, ld<V>(delta, i));
   }
 };
 
@@ -287,9 +312,9 @@ struct DcasgdaOp {
   using elem = float;
   float* data; float* bak; float* msq; const D* delta;
   float lr, lambda, rho, eps;
-  template <class V> __device__ __forceinline__ V step_at(int64_t i,
-                                                          V g) const {
-    V w = ld<V>(data, i), b = ld<V>(bak, i);
+  template <class V, bool KEEP = false>
+  __device__ __forceinline__ V step_at(int64_t i, V g) const {
+    V w = ld_shard<V, KEEP>(data, i), b = ld<V>(bak, i);
     V m = rho * ld<V>(msq, i) + (1.0f - rho) * g * g;
     st(msq, i, m);
     V lam = lambda * rsq(m + eps);
@@ -299,7 +324,7 @@ struct DcasgdaOp {
     return w;
   }
   template <class V> __device__ __forceinline__ V step(int64_t i) const {
-    return step_at<V>(i, ld<V>(delta, i));
+    return step_at<V, true>(i, ld<V>(delta, i));
   }
 };
 
@@ -322,9 +347,9 @@ struct AdamOp {
   using elem = T;
   T* data; T* m; T* v; const D* delta;
   T b1, omb1, b2, omb2, alpha, rbc2, decay, eps;
-  template <class V> __device__ __forceinline__ V step_at(int64_t i,
-                                                          V g) const {
-    V w = ld<V>(data, i), mm = ld<V>(m, i), vv = ld<V>(v, i);
+  template <class V, bool KEEP = false>
+  __device__ __forceinline__ V step_at(int64_t i, V g) const {
+    V w = ld_shard<V, KEEP>(data, i), mm = ld<V>(m, i), vv = ld<V>(v, i);
     mm = __builtin_elementwise_fma((V)b1, mm, omb1 * g);
     vv = __builtin_elementwise_fma((V)b2, vv, omb2 * g * g);
     V den = __builtin_elementwise_fma(__builtin_elementwise_sqrt(vv), (V)rbc2,
@@ -336,7 +361,7 @@ struct AdamOp {
     return w;
   }
   template <class V> __device__ __forceinline__ V step(int64_t i) const {
-    return step_at<V>(i, ld<V>(delta, i));
+    return step_at<V, true>(i, ld<V>(delta, i));
   }
 };
 
@@ -372,49 +397,76 @@ struct CopyOp {
 // AND out filled with the updated values).
 // `out` is the Get buffer, an array of O (the shard's type, or bf16) that
 // st views as V like the op's own arrays.
+//
+// `rev` (body launches only: start == 0, block a multiple of WAVE) makes
+// the pass descend: wave w of the grid-stride order takes the w-th 64
+// V-elements from the top, lanes still ascending inside them, so a wave
+// keeps its one contiguous request per access. Element j is computed from
+// element j of every array either way; only the order in which the
+// elements are visited changes. The launchers alternate it from one
+// whole-shard pass to the next (see the SWEEP note at launch_elem), so the
+// lines a pass touched last are the ones the next pass touches first,
+// while the Infinity Cache still holds them.
 template <class Op, class V, bool COPY, class O>
-__global__ void k_elem(Op op, O* __restrict__ out, int64_t start, int64_t n) {
+__global__ void k_elem(Op op, O* __restrict__ out, int64_t start, int64_t n,
+                       int rev) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  // whole waves mirror: the loop covers n rounded up to WAVE, and an index
+  // past n (the ragged wave) is skipped
+  int64_t n_pad = (n + (WAVE - 1)) & ~(int64_t)(WAVE - 1);
   for (int64_t i = start + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-       i < n; i += stride) {
-    V v = op.template step<V>(i);
-    if (COPY) st(out, i, v);
+       i < n_pad; i += stride) {
+    int64_t lane = threadIdx.x & (WAVE - 1);
+    int64_t j = rev ? n_pad - WAVE - i + 2 * lane : i;
+    if (j < n) {
+      V v = op.template step<V>(j);
+      if (COPY) st(out, j, v);
+    }
   }
 }
 
+// SWEEP: `rev` is the direction of the body launch (start == 0) of every
+// path below; the n%4 tail (one wave) ignores it. The caller alternates it
+// from one pass over the same arrays to the next (Updater._sweep). With
+// the shard loaded plainly (ld_shard) the last ~128 MiB of the shard that
+// pass k touched are read from the Infinity Cache by pass k+1 and
+// overwritten there before their write-back: 0.361 -> 0.292 ms per
+// fused sgd pass at 1e6x128 in the probe, against no change at all while
+// every access is non-temporal (profiles/sweep_direction.md).
+//
 // fp32: float4 body over n/4 vectors with the given grid cap and block,
 // then one wave over the n%4 scalar tail. Other types, and fp32 with
 // vec = false (a bf16 pointer that is not 8-byte aligned): scalar
 // grid-stride.
 template <bool COPY, class Op, class O>
 static void launch_elem(const Op& op, O* out, int64_t n, int cap, int block,
-                        hipStream_t s, bool vec = true) {
+                        hipStream_t s, bool vec = true, int rev = 0) {
   using T = typename Op::elem;
   if constexpr (std::is_same<T, float>::value) {
     if (vec) {
       int64_t n4 = n / 4;
       if (n4) k_elem<Op, v4f, COPY><<<grid_for_cap(n4, cap, block), block, 0,
-                                      s>>>(op, out, 0, n4);
+                                      s>>>(op, out, 0, n4, rev);
       if (n > n4 * 4) k_elem<Op, float, COPY><<<1, 64, 0, s>>>(op, out,
-                                                               n4 * 4, n);
+                                                               n4 * 4, n, 0);
       return;
     }
   }
   if (n > 0)
     k_elem<Op, T, COPY><<<grid_for_cap(n, cap, block), block, 0, s>>>(
-        op, out, 0, n);
+        op, out, 0, n, rev);
 }
 
-// fp32 updater launch: a non-null `out` selects the fused Add+Get form
-// with its fat-block geometry (COPY_BLOCK x COPY_GRID, see the sweep note
-// at the COPY_BLOCK define); otherwise BLOCK threads x `cap` blocks. The
-// bf16 forms keep the geometry of their fp32 siblings.
+// fp32 updater launch: a non-null `out` selects the fused Add+Get form.
+// Both forms run BLOCK threads x `cap` blocks (see the note at the
+// COPY_BLOCK define); the bf16 forms keep the geometry of their fp32
+// siblings.
 template <class Op, class O>
 static void launch_update(const Op& op, O* out, int64_t n, int cap,
-                          hipStream_t s) {
+                          hipStream_t s, int rev) {
   bool vec = vec_ok(op.delta) && vec_ok(out);
-  if (out) launch_elem<true>(op, out, n, COPY_GRID, COPY_BLOCK, s, vec);
-  else launch_elem<false>(op, (float*)nullptr, n, cap, BLOCK, s, vec);
+  if (out) launch_elem<true>(op, out, n, cap, BLOCK, s, vec, rev);
+  else launch_elem<false>(op, (float*)nullptr, n, cap, BLOCK, s, vec, rev);
 }
 
 extern "C" {
@@ -430,102 +482,107 @@ void mv_launch_copy(void* dst, const float* src, int wire, int64_t n,
 }
 
 void mv_launch_add(float* data, const void* delta, int wire, int64_t n,
-                   hipStream_t s) {
+                   hipStream_t s, int rev) {
   with_wire(wire, delta, nullptr, [&](auto* d, auto*) {
     launch_elem<false>(AddOp<float, ELEM_OF(d)>{data, d}, (float*)nullptr, n,
-                       UPD_GRID, BLOCK, s, vec_ok(d));
+                       UPD_GRID, BLOCK, s, vec_ok(d), rev);
   });
 }
-void mv_launch_add_f64(double* d, const double* x, int64_t n, hipStream_t s) {
+void mv_launch_add_f64(double* d, const double* x, int64_t n, hipStream_t s,
+                       int rev) {
   launch_elem<false>(AddOp<double>{d, x}, (double*)nullptr, n, ELEM_GRID,
-                     BLOCK, s);
+                     BLOCK, s, true, rev);
 }
-void mv_launch_add_i32(int32_t* d, const int32_t* x, int64_t n, hipStream_t s) {
+void mv_launch_add_i32(int32_t* d, const int32_t* x, int64_t n, hipStream_t s,
+                       int rev) {
   launch_elem<false>(AddOp<int32_t>{d, x}, (int32_t*)nullptr, n, ELEM_GRID,
-                     BLOCK, s);
+                     BLOCK, s, true, rev);
 }
-void mv_launch_add_i64(int64_t* d, const int64_t* x, int64_t n, hipStream_t s) {
+void mv_launch_add_i64(int64_t* d, const int64_t* x, int64_t n, hipStream_t s,
+                       int rev) {
   launch_elem<false>(AddOp<int64_t>{d, x}, (int64_t*)nullptr, n, ELEM_GRID,
-                     BLOCK, s);
+                     BLOCK, s, true, rev);
 }
 
 void mv_launch_sgd(float* data, const void* delta, void* out, int wire,
-                   float sign, int64_t n, hipStream_t s) {
+                   float sign, int64_t n, hipStream_t s, int rev) {
   with_wire(wire, delta, out, [&](auto* d, auto* o) {
-    launch_update(SgdOp<float, ELEM_OF(d)>{data, d, sign}, o, n, UPD_GRID, s);
+    launch_update(SgdOp<float, ELEM_OF(d)>{data, d, sign}, o, n, UPD_GRID, s,
+                  rev);
   });
 }
 void mv_launch_sgd_f64(double* d, const double* x, double* out, double sign,
-                       int64_t n, hipStream_t s) {
+                       int64_t n, hipStream_t s, int rev) {
   SgdOp<double> op{d, x, sign};
-  if (out) launch_elem<true>(op, out, n, STATE_GRID, BLOCK, s);
-  else launch_elem<false>(op, out, n, ELEM_GRID, BLOCK, s);
+  if (out) launch_elem<true>(op, out, n, STATE_GRID, BLOCK, s, true, rev);
+  else launch_elem<false>(op, out, n, ELEM_GRID, BLOCK, s, true, rev);
 }
 
 void mv_launch_momentum(float* data, float* m, const void* delta, void* out,
-                        int wire, float mu, int64_t n, hipStream_t s) {
+                        int wire, float mu, int64_t n, hipStream_t s, int rev) {
   with_wire(wire, delta, out, [&](auto* d, auto* o) {
     launch_update(MomentumOp<float, ELEM_OF(d)>{data, m, d, mu}, o, n,
-                  STATE_GRID, s);
+                  STATE_GRID, s, rev);
   });
 }
 void mv_launch_momentum_f64(double* d, double* m, const double* x, double mu,
-                            int64_t n, hipStream_t s) {
+                            int64_t n, hipStream_t s, int rev) {
   launch_elem<false>(MomentumOp<double>{d, m, x, mu}, (double*)nullptr, n,
-                     STATE_GRID, BLOCK, s);
+                     STATE_GRID, BLOCK, s, true, rev);
 }
 
 void mv_launch_adagrad(float* data, float* gsq, const void* delta, void* out,
                        int wire, float lr, float rho, float eps, int64_t n,
-                       hipStream_t s) {
+                       hipStream_t s, int rev) {
   with_wire(wire, delta, out, [&](auto* d, auto* o) {
     launch_update(AdagradOp<float, ELEM_OF(d)>{data, gsq, d, 1.0f / lr, rho,
                                                eps},
-                  o, n, STATE_GRID, s);
+                  o, n, STATE_GRID, s, rev);
   });
 }
 void mv_launch_adagrad_f64(double* d, double* g, const double* x, double lr,
-                           double rho, double eps, int64_t n, hipStream_t s) {
+                           double rho, double eps, int64_t n, hipStream_t s,
+                           int rev) {
   launch_elem<false>(AdagradOp<double>{d, g, x, 1.0 / lr, rho, eps},
-                     (double*)nullptr, n, STATE_GRID, BLOCK, s);
+                     (double*)nullptr, n, STATE_GRID, BLOCK, s, true, rev);
 }
 
 void mv_launch_dcasgd(float* data, float* bak, const void* delta, void* out,
                       int wire, float lr, float lambda, int64_t n,
-                      hipStream_t s) {
+                      hipStream_t s, int rev) {
   with_wire(wire, delta, out, [&](auto* d, auto* o) {
     launch_update(DcasgdOp<ELEM_OF(d)>{data, bak, d, lr, lambda}, o, n,
-                  STATE_GRID, s);
+                  STATE_GRID, s, rev);
   });
 }
 
 void mv_launch_dcasgda(float* data, float* bak, float* msq, const void* delta,
                        void* out, int wire, float lr, float lambda, float rho,
-                       float eps, int64_t n, hipStream_t s) {
+                       float eps, int64_t n, hipStream_t s, int rev) {
   with_wire(wire, delta, out, [&](auto* d, auto* o) {
     launch_update(DcasgdaOp<ELEM_OF(d)>{data, bak, msq, d, lr, lambda, rho,
                                         eps},
-                  o, n, STATE_GRID, s);
+                  o, n, STATE_GRID, s, rev);
   });
 }
 
-// Geometry is the other stateful updaters' STATE_GRID (COPY_BLOCK x
-// COPY_GRID with `out`): no grid sweep has been run for a 4-read/3-write
-// stream.
+// Geometry is the other stateful updaters' STATE_GRID: no grid sweep has
+// been run for a 4-read/3-write stream.
 void mv_launch_adam(float* data, float* m, float* v, const void* delta,
                     void* out, int wire, double b1, double b2, double step,
                     double rbc2, double decay, double eps, int64_t n,
-                    hipStream_t s) {
+                    hipStream_t s, int rev) {
   with_wire(wire, delta, out, [&](auto* d, auto* o) {
     launch_update(adam_op(data, m, v, d, b1, b2, step, rbc2, decay, eps), o,
-                  n, STATE_GRID, s);
+                  n, STATE_GRID, s, rev);
   });
 }
 void mv_launch_adam_f64(double* d, double* m, double* v, const double* x,
                         double b1, double b2, double step, double rbc2,
-                        double decay, double eps, int64_t n, hipStream_t s) {
+                        double decay, double eps, int64_t n, hipStream_t s,
+                        int rev) {
   launch_elem<false>(adam_op(d, m, v, x, b1, b2, step, rbc2, decay, eps),
-                     (double*)nullptr, n, STATE_GRID, BLOCK, s);
+                     (double*)nullptr, n, STATE_GRID, BLOCK, s, true, rev);
 }
 
 }  // extern "C"

@@ -39,7 +39,9 @@ to the in-tree HIP extension (multiverso_amd.ops) — fused read-modify-write
 kernels, float4-vectorized, grid-stride (memory-bound per the CDNA4 guide:
 the bound is HBM3E bytes, so fusing m/G state updates into the same pass
 halves traffic vs. composing torch ops). CPU fallback uses torch ops and
-is numerically identical in fp32.
+is numerically identical in fp32. Each whole-shard GPU pass runs in the
+opposite direction to the one before it (``Updater._sweep``), which lets the
+Infinity Cache serve the turning end of the shard and its state.
 
 bf16 wire format (tables built with ``wire_dtype=torch.bfloat16``): on a
 float32 shard every updater also takes a bfloat16 ``delta``, and
@@ -110,10 +112,25 @@ class Updater:
 
     def __init__(self, shard: torch.Tensor) -> None:
         self.shard = shard
+        # sweep direction of the next whole-shard GPU pass (see _sweep)
+        self.reverse = False
+
+    def _sweep(self) -> bool:
+        """Direction for one whole-shard GPU launch; flips the parity.
+
+        Consecutive passes over the shard (and its state) run in opposite
+        directions, so the lines a pass touched last are the first the next
+        pass touches, while the Infinity Cache still holds them. A hint
+        only: the kernels compute the same bits either way. Row-keyed ops,
+        store/load and the Get copy-out neither read nor flip it; the CPU
+        fallbacks ignore it."""
+        rev = self.reverse
+        self.reverse = not rev
+        return rev
 
     def update(self, delta: torch.Tensor, option: Optional[AddOption]) -> None:
         if self.shard.is_cuda:
-            _hip_ops().add_inplace(self.shard, delta)
+            _hip_ops().add_inplace(self.shard, delta, reverse=self._sweep())
         else:
             self.shard.add_(_widened(delta))
 
@@ -126,7 +143,8 @@ class Updater:
         the CPU fallback composes update + copy."""
         if self.shard.is_cuda and self.shard.dtype in (torch.float32,
                                                         torch.float64):
-            _hip_ops().sgd_copy_update(self.shard, delta, out, 1.0)
+            _hip_ops().sgd_copy_update(self.shard, delta, out, 1.0,
+                                       reverse=self._sweep())
         else:
             self.update(delta, option)
             out.copy_(self.shard)
@@ -141,14 +159,16 @@ class SGDUpdater(Updater):
 
     def update(self, delta: torch.Tensor, option: Optional[AddOption]) -> None:
         if self.shard.is_cuda:
-            _hip_ops().sgd_update(self.shard, delta)
+            _hip_ops().sgd_update(self.shard, delta,
+                                  reverse=self._sweep())
         else:
             self.shard.sub_(_widened(delta))
 
     def update_and_copy(self, delta, option, out) -> None:
         if self.shard.is_cuda and self.shard.dtype in (torch.float32,
                                                        torch.float64):
-            _hip_ops().sgd_copy_update(self.shard, delta, out, -1.0)
+            _hip_ops().sgd_copy_update(self.shard, delta, out, -1.0,
+                                       reverse=self._sweep())
         else:
             self.update(delta, option)
             out.copy_(self.shard)
@@ -165,7 +185,8 @@ class MomentumUpdater(Updater):
         mu = option.momentum if option else 0.0
         if self.shard.is_cuda:
             _hip_ops().momentum_update(self.shard, self.smooth_gradient,
-                                       delta, float(mu))
+                                       delta, float(mu),
+                                       reverse=self._sweep())
         else:
             self.smooth_gradient.mul_(mu).add_(_widened(delta),
                                                alpha=1.0 - mu)
@@ -175,7 +196,8 @@ class MomentumUpdater(Updater):
         if self.shard.is_cuda and self.shard.dtype == torch.float32:
             mu = option.momentum if option else 0.0
             _hip_ops().momentum_copy_update(self.shard, self.smooth_gradient,
-                                            delta, out, float(mu))
+                                            delta, out, float(mu),
+                                            reverse=self._sweep())
         else:
             self.update(delta, option)
             out.copy_(self.shard)
@@ -194,7 +216,8 @@ class AdaGradUpdater(Updater):
         lr, rho = opt.learning_rate, opt.rho
         if self.shard.is_cuda:
             _hip_ops().adagrad_update(self.shard, self.g_sqr, delta,
-                                      float(lr), float(rho), self.EPS)
+                                      float(lr), float(rho), self.EPS,
+                                      reverse=self._sweep())
         else:
             g = _widened(delta) / lr
             self.g_sqr.add_(g * g)
@@ -205,7 +228,8 @@ class AdaGradUpdater(Updater):
             opt = option or AddOption()
             _hip_ops().adagrad_copy_update(self.shard, self.g_sqr, delta,
                                            out, float(opt.learning_rate),
-                                           float(opt.rho), self.EPS)
+                                           float(opt.rho), self.EPS,
+                                           reverse=self._sweep())
         else:
             self.update(delta, option)
             out.copy_(self.shard)
@@ -243,7 +267,8 @@ class DCASGDUpdater(Updater):
         bak = self._backup(opt.worker_id)
         if self.shard.is_cuda and self.shard.dtype == torch.float32:
             _hip_ops().dcasgd_update(self.shard, bak, delta,
-                                     float(lr), float(lam))
+                                     float(lr), float(lam),
+                                     reverse=self._sweep())
         else:
             g = _widened(delta)
             self.shard.sub_(lr * (g + lam * g * g * (self.shard - bak)))
@@ -255,7 +280,8 @@ class DCASGDUpdater(Updater):
             bak = self._backup(opt.worker_id)
             _hip_ops().dcasgd_copy_update(self.shard, bak, delta, out,
                                           float(opt.learning_rate),
-                                          float(opt.lambda_))
+                                          float(opt.lambda_),
+                                          reverse=self._sweep())
         else:
             self.update(delta, option)
             out.copy_(self.shard)
@@ -280,7 +306,8 @@ class DCASGDAUpdater(DCASGDUpdater):
         if self.shard.is_cuda and self.shard.dtype == torch.float32:
             _hip_ops().dcasgda_update(self.shard, bak, self.mean_sqr, delta,
                                       float(lr), float(lam), float(rho),
-                                      self.EPS)
+                                      self.EPS,
+                                      reverse=self._sweep())
         else:
             g = _widened(delta)
             self.mean_sqr.mul_(rho).add_((1.0 - rho) * g * g)
@@ -296,7 +323,8 @@ class DCASGDAUpdater(DCASGDUpdater):
                                            delta, out,
                                            float(opt.learning_rate),
                                            float(opt.lambda_),
-                                           float(opt.rho), self.EPS)
+                                           float(opt.rho), self.EPS,
+                                           reverse=self._sweep())
         else:
             self.update(delta, option)
             out.copy_(self.shard)
@@ -364,7 +392,8 @@ class AdamUpdater(Updater):
         s = self.next_scalars(option)
         if self.shard.is_cuda:
             _hip_ops().adam_update(self.shard, self.exp_avg, self.exp_avg_sq,
-                                   delta, *s)
+                                   delta, *s,
+                                   reverse=self._sweep())
         else:
             self.torch_step(self.shard, self.exp_avg, self.exp_avg_sq,
                             _widened(delta), s)
@@ -373,7 +402,8 @@ class AdamUpdater(Updater):
         if self.shard.is_cuda and self.shard.dtype == torch.float32:
             _hip_ops().adam_copy_update(self.shard, self.exp_avg,
                                         self.exp_avg_sq, delta, out,
-                                        *self.next_scalars(option))
+                                        *self.next_scalars(option),
+                                        reverse=self._sweep())
         else:
             self.update(delta, option)
             out.copy_(self.shard)
