@@ -94,35 +94,16 @@ class SparseMatrixTable(MatrixTable):
 
     def add_rows(self, row_ids, values, option: Optional[AddOption] = None,
                  source_worker: Optional[int] = None) -> None:
-        self.flush()   # a deferred whole-table Add must land first
-        eng = self.engine
-        if eng is not None:
-            # keyed add served on arrival; the server-side hook above
-            # invalidates the touched rows for every worker
-            ids = torch.as_tensor(row_ids, dtype=torch.int64).cpu()
-            vals = values.to(self.device, self.dtype).contiguous()
-            from ..comm import Handle
-            with monitor("worker.add_rows"):
-                self._track(Handle(eng.keyed_add(
-                    self, ids, vals, self.num_col, option)))
-            return
-        ids = torch.as_tensor(row_ids, dtype=torch.int64)
-        vals = values.to(self.device, self.dtype).contiguous()
-        from ..comm import all_to_all_rows
-        with monitor("worker.add_rows"):
-            in_ids, in_vals, recv_sizes, _, _ = all_to_all_rows(
-                ids, vals.view(-1), self.spec, self.num_col,
-                device=self.device)
-            if in_ids.numel():
-                local = self._local_rows_of(in_ids)
-                with monitor("server.update_rows"):
-                    self._scatter_update_local(
-                        local, in_vals.view(-1, self.num_col), option)
-                # UpdateAddState: conservatively invalidate the touched
-                # rows for EVERY worker (the reference spares the adding
-                # worker, whose cache is pre-add anyway; invalidating all
-                # is never-stale-safe and costs one extra row re-pull)
-                self.up_to_date[:, local] = False
+        # on the async plane the server-side hook above invalidates the
+        # touched rows; on the sync plane _rows_added does
+        super().add_rows(row_ids, values, option)
+
+    def _rows_added(self, local_ids: torch.Tensor) -> None:
+        # UpdateAddState: conservatively invalidate the touched rows for
+        # EVERY worker (the reference spares the adding worker, whose cache
+        # is pre-add anyway; invalidating all is never-stale-safe and costs
+        # one extra row re-pull)
+        self.up_to_date[:, local_ids] = False
 
     def _filtered_value_exchange(self, served: torch.Tensor,
                                  send_rows, recv_rows) -> torch.Tensor:

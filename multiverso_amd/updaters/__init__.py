@@ -107,8 +107,32 @@ def _hip_ops():
     return ops.module(required=torch.cuda.is_available())
 
 
+_F32, _F64 = torch.float32, torch.float64
+
+
 class Updater:
-    name = "default"
+    """One rule, three forms: ``update`` (whole shard), ``update_and_copy``
+    (whole shard, fused with the Get copy-out) and ``update_rows`` (the rows
+    a keyed Add names). A subclass supplies
+
+    - ``_resolve(option)``: its state tensors and its scalars for one update,
+      in the order the kernels take them (the defaulting of ``option=None``
+      lives there);
+    - ``torch_step(w, *state, g, scalars)``: its formula in torch ops, in
+      place — the fallback of all three forms;
+    - the shard dtypes its HIP kernels cover, per form. Every other GPU
+      shard, and every CPU shard, takes ``torch_step``.
+
+    The extension's entry points are regular — ``X_update(data, *state,
+    delta, *scalars, reverse=)``, ``X_copy_update(data, *state, delta, out,
+    *scalars, reverse=)``, ``row_X_update(shard, *state, rows, vals,
+    *scalars, perm)`` — so ``_hip_update`` and ``_hip_rows`` dispatch by
+    ``name``; the updaters whose entry points differ override them."""
+
+    name: str
+    whole_dtypes = (_F32, _F64)
+    fused_dtypes = (_F32,)
+    keyed_dtypes = (_F32,)
 
     def __init__(self, shard: torch.Tensor) -> None:
         self.shard = shard
@@ -128,11 +152,52 @@ class Updater:
         self.reverse = not rev
         return rev
 
-    def update(self, delta: torch.Tensor, option: Optional[AddOption]) -> None:
-        if self.shard.is_cuda:
-            _hip_ops().add_inplace(self.shard, delta, reverse=self._sweep())
+    def _resolve(self, option: Optional[AddOption]):
+        """(state tensors, scalars) of one update under ``option``."""
+        raise NotImplementedError
+
+    def _hip_update(self, state, delta: torch.Tensor,
+                    out: Optional[torch.Tensor], scalars) -> None:
+        """One whole-shard launch; with ``out`` the fused Add+Get kernel."""
+        hip, rev = _hip_ops(), self._sweep()
+        if out is None:
+            getattr(hip, self.name + "_update")(
+                self.shard, *state, delta, *scalars, reverse=rev)
         else:
-            self.shard.add_(_widened(delta))
+            getattr(hip, self.name + "_copy_update")(
+                self.shard, *state, delta, out, *scalars, reverse=rev)
+
+    def _hip_rows(self, w, state, ids, vals, scalars,
+                  assume_unique: bool) -> None:
+        """k_row_update: value rows with the same id are summed in batch
+        order, then one step per distinct row."""
+        perm = None
+        if not assume_unique:
+            # equal ids adjacent, batch order kept inside each run; the
+            # kernel reads the payload through perm, so vals stay put
+            ids, perm = torch.sort(ids, stable=True)
+        getattr(_hip_ops(), f"row_{self.name}_update")(
+            w, *state, ids, vals, *scalars, perm)
+
+    def _torch_rows(self, w, state, ids, vals, scalars) -> None:
+        """The keyed semantics in torch ops: pre-sum duplicate rows, step
+        the gathered rows of the distinct ids, write them back."""
+        urows, inv = torch.unique(ids, return_inverse=True)
+        g = torch.zeros(urows.numel(), vals.size(1), dtype=w.dtype,
+                        device=w.device)
+        g.index_add_(0, inv, vals)
+        tensors = (w, *state)
+        picked = [t[urows] for t in tensors]
+        self.torch_step(*picked, g, scalars)
+        for t, p in zip(tensors, picked):
+            t[urows] = p
+
+    def update(self, delta: torch.Tensor, option: Optional[AddOption]) -> None:
+        state, scalars = self._resolve(option)
+        if self.shard.is_cuda and self.shard.dtype in self.whole_dtypes:
+            self._hip_update(state, delta, None, scalars)
+        else:
+            self.torch_step(self.shard, *state, _widened(delta), scalars)
 
     def update_and_copy(self, delta: torch.Tensor,
                         option: Optional[AddOption],
@@ -140,38 +205,98 @@ class Updater:
         """Fused Add+Get (single-rank fast path): apply the update AND
         stream the updated shard into ``out`` in the same pass — saves
         the Get's shard re-read. Every updater has a fused HIP kernel;
-        the CPU fallback composes update + copy."""
-        if self.shard.is_cuda and self.shard.dtype in (torch.float32,
-                                                        torch.float64):
-            _hip_ops().sgd_copy_update(self.shard, delta, out, 1.0,
-                                       reverse=self._sweep())
+        the fallback composes update + copy."""
+        if self.shard.is_cuda and self.shard.dtype in self.fused_dtypes:
+            state, scalars = self._resolve(option)
+            self._hip_update(state, delta, out, scalars)
         else:
             self.update(delta, option)
             out.copy_(self.shard)
+
+    def update_rows(self, local_ids: torch.Tensor, vals2d: torch.Tensor,
+                    option: Optional[AddOption],
+                    assume_unique: bool = False) -> None:
+        """Row-keyed Add on the rows ``local_ids`` of the shard, seen as
+        [rows, vals2d.size(1)] (the per-row updater dispatch of
+        matrix_table.cpp:406-412). Duplicate ids of one batch are summed,
+        then the rule steps once per distinct row; weights and state of
+        other rows stay as they are. ``option`` defaults as in ``update``.
+        A batch that brings this shard no rows is no update."""
+        if not local_ids.numel():
+            return
+        from ..configure import get_flag
+        if get_flag("deterministic") and not assume_unique:
+            # fixed reduction order: pre-sum duplicate rows (sorted
+            # segments) and update without atomics
+            order = torch.argsort(local_ids, stable=True)
+            v = vals2d[order]
+            local_ids, counts = torch.unique_consecutive(
+                local_ids[order], return_counts=True)
+            # fp64 cumsum-diff segmented sum: fixed order, no atomics
+            cs = torch.zeros(v.size(0) + 1, v.size(1), dtype=torch.float64,
+                             device=v.device)
+            torch.cumsum(v.to(torch.float64), 0, out=cs[1:])
+            ends = counts.cumsum(0)
+            # the shard's dtype, not v's: a bf16-wire sum stays fp32
+            vals2d = (cs[ends] - cs[ends - counts]).to(self.shard.dtype)
+            assume_unique = True
+        cols = vals2d.size(1)
+        state, scalars = self._resolve(option)
+        w, state = self.shard.view(-1, cols), [s.view(-1, cols) for s in state]
+        if self.shard.is_cuda and self.shard.dtype in self.keyed_dtypes:
+            # a bf16-wire payload reaches the kernel as it is
+            self._hip_rows(w, state, local_ids, vals2d.contiguous(), scalars,
+                           assume_unique)
+        else:
+            self._torch_rows(w, state, local_ids, vals2d.to(w.dtype), scalars)
 
     def access(self, out: torch.Tensor) -> None:
         """K7: shard copy-out (updater.cpp:32-36)."""
         out.copy_(self.shard)
 
 
-class SGDUpdater(Updater):
+class DefaultUpdater(Updater):
+    """``data += sign * delta``: no state, no scalars, and entry points of
+    its own (K1/K2 whole, one signed fused kernel, the K5 scatter-add)."""
+
+    name = "default"
+    sign = 1.0
+    whole_dtypes = (_F32, _F64, torch.int32, torch.int64)
+    fused_dtypes = (_F32, _F64)
+
+    def _resolve(self, option):
+        return (), ()
+
+    @staticmethod
+    def torch_step(w: torch.Tensor, g: torch.Tensor, scalars) -> None:
+        w.add_(g)
+
+    def _hip_update(self, state, delta, out, scalars) -> None:
+        hip, rev = _hip_ops(), self._sweep()
+        if out is not None:
+            hip.sgd_copy_update(self.shard, delta, out, self.sign,
+                                reverse=rev)
+        elif self.sign > 0:
+            hip.add_inplace(self.shard, delta, reverse=rev)
+        else:
+            hip.sgd_update(self.shard, delta, reverse=rev)
+
+    def _hip_rows(self, w, state, ids, vals, scalars, assume_unique) -> None:
+        # atomic scatter-add: duplicates need no pre-sum
+        _hip_ops().row_scatter_add(w, ids, vals, self.sign, assume_unique)
+
+    def _torch_rows(self, w, state, ids, vals, scalars) -> None:
+        w.index_add_(0, ids, vals * self.sign)
+
+
+class SGDUpdater(DefaultUpdater):
     name = "sgd"
+    sign = -1.0
+    whole_dtypes = (_F32, _F64)
 
-    def update(self, delta: torch.Tensor, option: Optional[AddOption]) -> None:
-        if self.shard.is_cuda:
-            _hip_ops().sgd_update(self.shard, delta,
-                                  reverse=self._sweep())
-        else:
-            self.shard.sub_(_widened(delta))
-
-    def update_and_copy(self, delta, option, out) -> None:
-        if self.shard.is_cuda and self.shard.dtype in (torch.float32,
-                                                       torch.float64):
-            _hip_ops().sgd_copy_update(self.shard, delta, out, -1.0,
-                                       reverse=self._sweep())
-        else:
-            self.update(delta, option)
-            out.copy_(self.shard)
+    @staticmethod
+    def torch_step(w: torch.Tensor, g: torch.Tensor, scalars) -> None:
+        w.sub_(g)
 
 
 class MomentumUpdater(Updater):
@@ -181,26 +306,15 @@ class MomentumUpdater(Updater):
         super().__init__(shard)
         self.smooth_gradient = torch.zeros_like(shard)
 
-    def update(self, delta: torch.Tensor, option: Optional[AddOption]) -> None:
-        mu = option.momentum if option else 0.0
-        if self.shard.is_cuda:
-            _hip_ops().momentum_update(self.shard, self.smooth_gradient,
-                                       delta, float(mu),
-                                       reverse=self._sweep())
-        else:
-            self.smooth_gradient.mul_(mu).add_(_widened(delta),
-                                               alpha=1.0 - mu)
-            self.shard.sub_(self.smooth_gradient)
+    def _resolve(self, option):
+        opt = option or AddOption()   # momentum defaults to 0.0
+        return (self.smooth_gradient,), (float(opt.momentum),)
 
-    def update_and_copy(self, delta, option, out) -> None:
-        if self.shard.is_cuda and self.shard.dtype == torch.float32:
-            mu = option.momentum if option else 0.0
-            _hip_ops().momentum_copy_update(self.shard, self.smooth_gradient,
-                                            delta, out, float(mu),
-                                            reverse=self._sweep())
-        else:
-            self.update(delta, option)
-            out.copy_(self.shard)
+    @staticmethod
+    def torch_step(w, m, g, scalars) -> None:
+        mu, = scalars
+        m.mul_(mu).add_(g, alpha=1.0 - mu)
+        w.sub_(m)
 
 
 class AdaGradUpdater(Updater):
@@ -211,28 +325,23 @@ class AdaGradUpdater(Updater):
         super().__init__(shard)
         self.g_sqr = torch.zeros_like(shard)
 
-    def update(self, delta: torch.Tensor, option: Optional[AddOption]) -> None:
+    def _resolve(self, option):
         opt = option or AddOption()
-        lr, rho = opt.learning_rate, opt.rho
-        if self.shard.is_cuda:
-            _hip_ops().adagrad_update(self.shard, self.g_sqr, delta,
-                                      float(lr), float(rho), self.EPS,
-                                      reverse=self._sweep())
-        else:
-            g = _widened(delta) / lr
-            self.g_sqr.add_(g * g)
-            self.shard.sub_(rho * g / torch.sqrt(self.g_sqr + self.EPS))
+        return (self.g_sqr,), (float(opt.learning_rate), float(opt.rho),
+                               self.EPS)
 
-    def update_and_copy(self, delta, option, out) -> None:
-        if self.shard.is_cuda and self.shard.dtype == torch.float32:
-            opt = option or AddOption()
-            _hip_ops().adagrad_copy_update(self.shard, self.g_sqr, delta,
-                                           out, float(opt.learning_rate),
-                                           float(opt.rho), self.EPS,
-                                           reverse=self._sweep())
-        else:
-            self.update(delta, option)
-            out.copy_(self.shard)
+    @staticmethod
+    def torch_step(w, gsq, g, scalars) -> None:
+        lr, rho, eps = scalars
+        g = g / lr
+        gsq.add_(g * g)
+        w.sub_(rho * g / torch.sqrt(gsq + eps))
+
+    def _hip_rows(self, w, state, ids, vals, scalars, assume_unique) -> None:
+        # the keyed K15 kernel: duplicate rows race benignly via atomics
+        # and keep the G accumulate, so no sort and no perm
+        _hip_ops().row_scatter_adagrad(w, *state, ids, vals, *scalars,
+                                       assume_unique)
 
 
 class DCASGDUpdater(Updater):
@@ -249,6 +358,7 @@ class DCASGDUpdater(Updater):
     lazily initialized to the shard's current values."""
 
     name = "dcasgd"
+    whole_dtypes = (_F32,)
 
     def __init__(self, shard: torch.Tensor) -> None:
         super().__init__(shard)
@@ -261,30 +371,16 @@ class DCASGDUpdater(Updater):
             self._bak[worker_id] = b
         return b
 
-    def update(self, delta: torch.Tensor, option: Optional[AddOption]) -> None:
+    def _resolve(self, option):
         opt = option or AddOption()
-        lr, lam = opt.learning_rate, opt.lambda_
-        bak = self._backup(opt.worker_id)
-        if self.shard.is_cuda and self.shard.dtype == torch.float32:
-            _hip_ops().dcasgd_update(self.shard, bak, delta,
-                                     float(lr), float(lam),
-                                     reverse=self._sweep())
-        else:
-            g = _widened(delta)
-            self.shard.sub_(lr * (g + lam * g * g * (self.shard - bak)))
-            bak.copy_(self.shard)
+        return ((self._backup(opt.worker_id),),
+                (float(opt.learning_rate), float(opt.lambda_)))
 
-    def update_and_copy(self, delta, option, out) -> None:
-        if self.shard.is_cuda and self.shard.dtype == torch.float32:
-            opt = option or AddOption()
-            bak = self._backup(opt.worker_id)
-            _hip_ops().dcasgd_copy_update(self.shard, bak, delta, out,
-                                          float(opt.learning_rate),
-                                          float(opt.lambda_),
-                                          reverse=self._sweep())
-        else:
-            self.update(delta, option)
-            out.copy_(self.shard)
+    @staticmethod
+    def torch_step(w, bak, g, scalars) -> None:
+        lr, lam = scalars
+        w.sub_(lr * (g + lam * g * g * (w - bak)))
+        bak.copy_(w)
 
 
 class DCASGDAUpdater(DCASGDUpdater):
@@ -299,35 +395,19 @@ class DCASGDAUpdater(DCASGDUpdater):
         super().__init__(shard)
         self.mean_sqr = torch.zeros_like(shard)
 
-    def update(self, delta: torch.Tensor, option: Optional[AddOption]) -> None:
+    def _resolve(self, option):
         opt = option or AddOption()
-        lr, lam, rho = opt.learning_rate, opt.lambda_, opt.rho
-        bak = self._backup(opt.worker_id)
-        if self.shard.is_cuda and self.shard.dtype == torch.float32:
-            _hip_ops().dcasgda_update(self.shard, bak, self.mean_sqr, delta,
-                                      float(lr), float(lam), float(rho),
-                                      self.EPS,
-                                      reverse=self._sweep())
-        else:
-            g = _widened(delta)
-            self.mean_sqr.mul_(rho).add_((1.0 - rho) * g * g)
-            lam_t = lam / torch.sqrt(self.mean_sqr + self.EPS)
-            self.shard.sub_(lr * (g + lam_t * g * g * (self.shard - bak)))
-            bak.copy_(self.shard)
+        return ((self._backup(opt.worker_id), self.mean_sqr),
+                (float(opt.learning_rate), float(opt.lambda_),
+                 float(opt.rho), self.EPS))
 
-    def update_and_copy(self, delta, option, out) -> None:
-        if self.shard.is_cuda and self.shard.dtype == torch.float32:
-            opt = option or AddOption()
-            bak = self._backup(opt.worker_id)
-            _hip_ops().dcasgda_copy_update(self.shard, bak, self.mean_sqr,
-                                           delta, out,
-                                           float(opt.learning_rate),
-                                           float(opt.lambda_),
-                                           float(opt.rho), self.EPS,
-                                           reverse=self._sweep())
-        else:
-            self.update(delta, option)
-            out.copy_(self.shard)
+    @staticmethod
+    def torch_step(w, bak, msq, g, scalars) -> None:
+        lr, lam, rho, eps = scalars
+        msq.mul_(rho).add_((1.0 - rho) * g * g)
+        lam_t = lam / torch.sqrt(msq + eps)
+        w.sub_(lr * (g + lam_t * g * g * (w - bak)))
+        bak.copy_(w)
 
 
 class AdamUpdater(Updater):
@@ -388,29 +468,12 @@ class AdamUpdater(Updater):
         v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
         w.addcdiv_(m, v.sqrt().mul_(rbc2).add_(eps), value=-step)
 
-    def update(self, delta: torch.Tensor, option: Optional[AddOption]) -> None:
-        s = self.next_scalars(option)
-        if self.shard.is_cuda:
-            _hip_ops().adam_update(self.shard, self.exp_avg, self.exp_avg_sq,
-                                   delta, *s,
-                                   reverse=self._sweep())
-        else:
-            self.torch_step(self.shard, self.exp_avg, self.exp_avg_sq,
-                            _widened(delta), s)
-
-    def update_and_copy(self, delta, option, out) -> None:
-        if self.shard.is_cuda and self.shard.dtype == torch.float32:
-            _hip_ops().adam_copy_update(self.shard, self.exp_avg,
-                                        self.exp_avg_sq, delta, out,
-                                        *self.next_scalars(option),
-                                        reverse=self._sweep())
-        else:
-            self.update(delta, option)
-            out.copy_(self.shard)
+    def _resolve(self, option):
+        return (self.exp_avg, self.exp_avg_sq), self.next_scalars(option)
 
 
 _REGISTRY: Dict[str, Type[Updater]] = {
-    "default": Updater,
+    "default": DefaultUpdater,
     "sgd": SGDUpdater,
     "momentum": MomentumUpdater,
     "adagrad": AdaGradUpdater,

@@ -34,7 +34,9 @@ def state_of(t, name, worker_id=0):
     out = [t.shard.clone()]
     if name == "momentum":
         out.append(u.smooth_gradient.view(shape).clone())
-    else:
+    elif name == "adagrad":
+        out.append(u.g_sqr.view(shape).clone())
+    elif name in ("dcasgd", "dcasgda"):
         out.append(u._backup(worker_id).view(shape).clone())
     if name == "dcasgda":
         out.append(u.mean_sqr.view(shape).clone())
@@ -142,7 +144,7 @@ def test_option_none_and_empty_batch(env, name):
         assert torch.equal(x, y)
 
 
-@pytest.mark.parametrize("name", STATEFUL)
+@pytest.mark.parametrize("name", STATEFUL + ["default", "sgd", "adagrad"])
 def test_all_rows_equals_whole_table(env, name):
     R, C = 9, 3
     g = torch.Generator().manual_seed(11)
