@@ -394,6 +394,13 @@ class WordEmbedding:
         z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
         return (z ^ (z >> 31)) & 0x7FFFFFFFFFFFFFFF
 
+    def _kernel_lr(self) -> float:
+        """The kernels' single rate: adagrad steps by the initial rate
+        (wordembedding.cpp:101-165), only the plain step decays."""
+        if self.opt.use_adagrad:
+            return self.opt.init_learning_rate
+        return self.learning_rate
+
     def _train_kernel_ns(self, in_buf, out_buf, in_gsq, out_gsq,
                          in_local, in_off, centers, pool):
         """NS fast path: negatives generated in-kernel from `pool`.
@@ -411,7 +418,7 @@ class WordEmbedding:
         if g_total <= step:
             hip.w2v_train_ns(in_buf, out_buf, igq, ogq, in_local, in_off,
                              centers, pool, self.opt.negative_num,
-                             self._next_seed(), self.learning_rate,
+                             self._next_seed(), self._kernel_lr(),
                              self.opt.use_adagrad, self.opt.atomic_updates)
             return
         gs = list(range(0, g_total, step)) + [g_total]
@@ -425,7 +432,7 @@ class WordEmbedding:
                              (in_off[g0:g1 + 1] - i0).contiguous(),
                              centers[g0:g1].contiguous(), pool,
                              self.opt.negative_num, self._next_seed(),
-                             self.learning_rate, self.opt.use_adagrad,
+                             self._kernel_lr(), self.opt.use_adagrad,
                              self.opt.atomic_updates)
 
     def _train_kernel(self, in_buf, out_buf, in_gsq, out_gsq,
@@ -444,7 +451,7 @@ class WordEmbedding:
                 # single launch: no slicing, no host sync
                 hip.w2v_train(in_buf, out_buf, igq, ogq,
                               in_local, in_off, out_local, out_label,
-                              out_off, self.learning_rate,
+                              out_off, self._kernel_lr(),
                               self.opt.use_adagrad,
                               self.opt.atomic_updates)
                 return
@@ -463,7 +470,7 @@ class WordEmbedding:
                               out_local[o0:o1].contiguous(),
                               out_label[o0:o1].contiguous(),
                               (out_off[g0:g1 + 1] - o0).contiguous(),
-                              self.learning_rate, self.opt.use_adagrad,
+                              self._kernel_lr(), self.opt.use_adagrad,
                               self.opt.atomic_updates)
         else:
             _w2v_train_torch(in_buf, out_buf, in_gsq, out_gsq, in_local,
@@ -533,7 +540,9 @@ def _w2v_train_torch(in_buf, out_buf, in_gsq, out_gsq, in_idx, in_off,
         ii = in_idx[in_off_l[g]:in_off_l[g + 1]]
         oo = out_idx[out_off_l[g]:out_off_l[g + 1]]
         ll = out_label[out_off_l[g]:out_off_l[g + 1]]
-        h = in_buf[ii].mean(dim=0)
+        # no inputs: h = 0 as in the kernel (mean of nothing is NaN)
+        h = (in_buf[ii].mean(dim=0) if ii.numel()
+             else torch.zeros_like(in_buf[0]))
         err = torch.zeros_like(h)
         for j in range(oo.numel()):
             r = int(oo[j])

@@ -523,6 +523,14 @@ void w2v_train(torch::Tensor in_emb, torch::Tensor out_emb,
               out_idx.scalar_type() == torch::kInt64, "idx must be int64");
   TORCH_CHECK(in_off.scalar_type() == torch::kInt32 &&
               out_off.scalar_type() == torch::kInt32, "offsets must be int32");
+  // the kernel takes these as raw device pointers
+  check_dev(in_idx, "in_idx", torch::kInt64);
+  check_dev(out_idx, "out_idx", torch::kInt64);
+  check_dev(in_off, "in_off", torch::kInt32);
+  check_dev(out_off, "out_off", torch::kInt32);
+  TORCH_CHECK(in_off.numel() >= 1, "in_off needs at least one entry");
+  TORCH_CHECK(out_idx.numel() == out_label.numel(),
+              "out_idx/out_label mismatch");
   int64_t G = in_off.numel() - 1;
   TORCH_CHECK(out_off.numel() - 1 == G, "group count mismatch");
   float *igq = nullptr, *ogq = nullptr;
@@ -554,10 +562,17 @@ void w2v_train_ns(torch::Tensor in_emb, torch::Tensor out_emb,
   TORCH_CHECK(in_idx.scalar_type() == torch::kInt64 &&
               centers.scalar_type() == torch::kInt64 &&
               pool.scalar_type() == torch::kInt64, "ids must be int64");
+  // the kernel takes these as raw device pointers
+  check_dev(in_idx, "in_idx", torch::kInt64);
+  check_dev(centers, "centers", torch::kInt64);
+  check_dev(pool, "pool", torch::kInt64);
+  TORCH_CHECK(neg >= 0, "neg must be >= 0");
   const int* in_off_ptr = nullptr;
   if (in_off_opt.has_value()) {
     TORCH_CHECK(in_off_opt->scalar_type() == torch::kInt32,
                 "offsets must be int32");
+    check_dev(*in_off_opt, "in_off", torch::kInt32);
+    TORCH_CHECK(in_off_opt->numel() >= 1, "in_off needs at least one entry");
     TORCH_CHECK(in_off_opt->numel() - 1 == centers.numel(),
                 "centers/group count mismatch");
     in_off_ptr = in_off_opt->data_ptr<int>();
