@@ -238,6 +238,8 @@ class FTRLObjective(Objective):
         w = self.reconstruct_w(zn_rows)
         p = torch.sigmoid(_scores(batch, w))
         diff = p - _one_hot(batch.labels, O)
+        if batch.weights is not None:
+            diff = diff * batch.weights.unsqueeze(1)
         g = batch.vals.unsqueeze(1) * diff[batch.sample_ids()]  # delta_g
         g2 = g * g
         n = torch.clamp(zn_rows[:, O:], min=0.0)

@@ -599,6 +599,21 @@ void w2v_train_ns(torch::Tensor in_emb, torch::Tensor out_emb,
                    cur_stream());
 }
 
+// The sparse logreg kernels read keys and ptr through raw device pointers:
+// both on the GPU and contiguous, one value per key, ptr with its leading
+// entry. Returns the batch size. Key range and ptr's monotonicity lie in
+// device memory and are not checked (that would take a sync).
+int64_t check_csr(const torch::Tensor& keys, const torch::Tensor& vals,
+                  const torch::Tensor& ptr) {
+  TORCH_CHECK(keys.scalar_type() == torch::kInt64 && keys.is_cuda() &&
+              keys.is_contiguous(), "keys must be contiguous int64 on GPU");
+  TORCH_CHECK(ptr.scalar_type() == torch::kInt32 && ptr.is_cuda() &&
+              ptr.is_contiguous(), "ptr must be contiguous int32 on GPU");
+  TORCH_CHECK(ptr.numel() >= 1, "ptr needs at least one entry");
+  TORCH_CHECK(keys.numel() == vals.numel(), "keys/vals mismatch");
+  return ptr.numel() - 1;
+}
+
 void lr_sigmoid_forward(torch::Tensor w, torch::Tensor keys,
                         torch::Tensor vals, torch::Tensor ptr,
                         torch::Tensor labels,
@@ -606,12 +621,9 @@ void lr_sigmoid_forward(torch::Tensor w, torch::Tensor keys,
                         torch::Tensor err, torch::Tensor loss) {
   check_f32(w, "w"); check_f32(vals, "vals"); check_f32(labels, "labels");
   check_f32(err, "err"); check_f32(loss, "loss");
-  TORCH_CHECK(keys.scalar_type() == torch::kInt64, "keys must be int64");
-  TORCH_CHECK(ptr.scalar_type() == torch::kInt32, "ptr must be int32");
-  int64_t B = ptr.numel() - 1;
+  int64_t B = check_csr(keys, vals, ptr);
   TORCH_CHECK(labels.numel() == B && err.numel() == B && loss.numel() == B,
               "batch size mismatch");
-  TORCH_CHECK(keys.numel() == vals.numel(), "keys/vals mismatch");
   const float* wp = nullptr;
   if (wts.has_value()) {
     check_f32(*wts, "wts");
@@ -630,9 +642,7 @@ void lr_sigmoid_scatter(torch::Tensor w, torch::Tensor keys,
                         torch::Tensor err, double lr, int64_t reg_type,
                         double reg_coef) {
   check_f32(w, "w"); check_f32(vals, "vals"); check_f32(err, "err");
-  TORCH_CHECK(keys.scalar_type() == torch::kInt64, "keys must be int64");
-  TORCH_CHECK(ptr.scalar_type() == torch::kInt32, "ptr must be int32");
-  int64_t B = ptr.numel() - 1;
+  int64_t B = check_csr(keys, vals, ptr);
   TORCH_CHECK(err.numel() == B, "err size mismatch");
   mv_launch_lr_sigmoid_scatter(w.data_ptr<float>(), keys.data_ptr<int64_t>(),
                                vals.data_ptr<float>(), ptr.data_ptr<int>(),
@@ -648,14 +658,12 @@ void lr_softmax_forward(torch::Tensor w, torch::Tensor keys,
                         torch::Tensor err, torch::Tensor loss, int64_t K) {
   check_f32(w, "w"); check_f32(vals, "vals"); check_f32(labels, "labels");
   check_f32(err, "err"); check_f32(loss, "loss");
-  TORCH_CHECK(keys.scalar_type() == torch::kInt64, "keys must be int64");
-  TORCH_CHECK(ptr.scalar_type() == torch::kInt32, "ptr must be int32");
   TORCH_CHECK(K >= 2 && K <= 64,
               "fused softmax supports 2..64 classes (got ", K, ")");
-  int64_t B = ptr.numel() - 1;
+  TORCH_CHECK(w.numel() % K == 0, "w must hold whole rows of K");
+  int64_t B = check_csr(keys, vals, ptr);
   TORCH_CHECK(labels.numel() == B && loss.numel() == B, "batch mismatch");
   TORCH_CHECK(err.numel() == B * K, "err must be [B, K]");
-  TORCH_CHECK(keys.numel() == vals.numel(), "keys/vals mismatch");
   const float* wp = nullptr;
   if (wts.has_value()) {
     check_f32(*wts, "wts");
@@ -674,9 +682,10 @@ void lr_softmax_scatter(torch::Tensor w, torch::Tensor keys,
                         torch::Tensor err, double lr, int64_t reg_type,
                         double reg_coef, int64_t K) {
   check_f32(w, "w"); check_f32(vals, "vals"); check_f32(err, "err");
-  TORCH_CHECK(keys.scalar_type() == torch::kInt64, "keys must be int64");
-  TORCH_CHECK(ptr.scalar_type() == torch::kInt32, "ptr must be int32");
-  int64_t B = ptr.numel() - 1;
+  TORCH_CHECK(K >= 2 && K <= 64,
+              "fused softmax supports 2..64 classes (got ", K, ")");
+  TORCH_CHECK(w.numel() % K == 0, "w must hold whole rows of K");
+  int64_t B = check_csr(keys, vals, ptr);
   TORCH_CHECK(err.numel() == B * K, "err must be [B, K]");
   mv_launch_lr_softmax_scatter(w.data_ptr<float>(), keys.data_ptr<int64_t>(),
                                vals.data_ptr<float>(), ptr.data_ptr<int>(),
@@ -692,16 +701,17 @@ void lr_ftrl_forward(torch::Tensor zn, torch::Tensor keys,
                      double beta, double l1, double l2, int64_t K) {
   check_f32(zn, "zn"); check_f32(vals, "vals"); check_f32(labels, "labels");
   check_f32(err, "err"); check_f32(loss, "loss");
-  TORCH_CHECK(keys.scalar_type() == torch::kInt64, "keys must be int64");
-  TORCH_CHECK(ptr.scalar_type() == torch::kInt32, "ptr must be int32");
   TORCH_CHECK(K >= 1 && K <= 32,
               "fused FTRL supports 1..32 outputs (got ", K, ")");
-  int64_t B = ptr.numel() - 1;
+  TORCH_CHECK(zn.numel() % (2 * K) == 0,
+              "zn must hold whole rows of 2*K (z | n)");
+  int64_t B = check_csr(keys, vals, ptr);
   TORCH_CHECK(labels.numel() == B && loss.numel() == B, "batch mismatch");
   TORCH_CHECK(err.numel() == B * K, "err must be [B, K]");
   const float* wp = nullptr;
   if (wts.has_value()) {
     check_f32(*wts, "wts");
+    TORCH_CHECK(wts->numel() == B, "weights size mismatch");
     wp = wts->data_ptr<float>();
   }
   mv_launch_lr_ftrl_fwd(zn.data_ptr<float>(), keys.data_ptr<int64_t>(),
@@ -768,9 +778,11 @@ void lr_ftrl_scatter(torch::Tensor zn, torch::Tensor keys,
                      torch::Tensor err, double alpha, double beta, double l1,
                      double l2, int64_t K) {
   check_f32(zn, "zn"); check_f32(vals, "vals"); check_f32(err, "err");
-  TORCH_CHECK(keys.scalar_type() == torch::kInt64, "keys must be int64");
-  TORCH_CHECK(ptr.scalar_type() == torch::kInt32, "ptr must be int32");
-  int64_t B = ptr.numel() - 1;
+  TORCH_CHECK(K >= 1 && K <= 32,
+              "fused FTRL supports 1..32 outputs (got ", K, ")");
+  TORCH_CHECK(zn.numel() % (2 * K) == 0,
+              "zn must hold whole rows of 2*K (z | n)");
+  int64_t B = check_csr(keys, vals, ptr);
   TORCH_CHECK(err.numel() == B * K, "err must be [B, K]");
   mv_launch_lr_ftrl_scatter(zn.data_ptr<float>(), keys.data_ptr<int64_t>(),
                             vals.data_ptr<float>(), ptr.data_ptr<int>(),

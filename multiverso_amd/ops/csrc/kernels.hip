@@ -1655,6 +1655,7 @@ __global__ void k_lr_ftrl_fwd(const float* __restrict__ zn,
     for (int k = 0; k < K; ++k)
 #pragma unroll
       for (int sh = 32; sh; sh >>= 1) l[k] += __shfl_xor(l[k], sh, 64);
+    float ll = 0.f;
     if (lane < KK) {
       float mine = 0.f;
 #pragma unroll
@@ -1665,14 +1666,14 @@ __global__ void k_lr_ftrl_fwd(const float* __restrict__ zn,
       float yk = (KK == 1) ? labels[i] : (float)(lane == y);
       float wt = wts ? wts[i] : 1.f;
       err[(int64_t)i * KK + lane] = (p - yk) * wt;
-      if (lane == 0) {
-        // binary NLL on class-0 probability (torch path parity)
-        float pp = p;
-        float yy = yk;
-        loss[i] = -(yy * logf(pp + 1e-12f)
-                    + (1.f - yy) * logf(1.f - pp + 1e-12f));
-      }
+      ll = -(yk * logf(p + 1e-12f) + (1.f - yk) * logf(1.f - p + 1e-12f));
     }
+    // binary NLL summed over the KK outputs, as Objective.loss does: lanes
+    // >= KK hold 0 and KK <= K, so the shifts below K bring every term to
+    // lane 0 (none at K == 1)
+    for (int sh = 32; sh; sh >>= 1)
+      if (sh < K) ll += __shfl_xor(ll, sh, 64);
+    if (lane == 0) loss[i] = ll;
   }
 }
 
