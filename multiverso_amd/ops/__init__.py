@@ -41,9 +41,12 @@ def build(verbose: bool = False) -> str:
 
     kernels_src = os.path.join(_CSRC, "kernels.hip")
     kernels_obj = os.path.join(_BUILD, "kernels.hip.o")
-    # Rebuild the pure-HIP object only when the source is newer.
+    # Rebuild the pure-HIP object only when the source, or the launcher
+    # declarations it includes, is newer.
+    newest = max(os.path.getmtime(p) for p in
+                 (kernels_src, os.path.join(_CSRC, "launchers.h")))
     if (not os.path.exists(kernels_obj)
-            or os.path.getmtime(kernels_src) > os.path.getmtime(kernels_obj)):
+            or newest > os.path.getmtime(kernels_obj)):
         cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
                "-c", kernels_src, "-o", kernels_obj]
         if verbose:

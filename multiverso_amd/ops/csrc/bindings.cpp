@@ -9,100 +9,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <cstdint>
 
-extern "C" {
-// elementwise updaters: a non-null `out` (the pointer before `wire`)
-// selects the fused Add+Get form. The fp32 forms take the delta and `out`
-// as void* and, in `wire`, the WIRE_* bits that say which holds bf16. The
-// trailing int of the updaters is the sweep direction (1 = descending): a
-// performance hint, the result is the same either way.
-void mv_launch_copy(void*, const float*, int, int64_t, hipStream_t);
-void mv_launch_add(float*, const void*, int, int64_t, hipStream_t, int);
-void mv_launch_add_f64(double*, const double*, int64_t, hipStream_t, int);
-void mv_launch_add_i32(int32_t*, const int32_t*, int64_t, hipStream_t, int);
-void mv_launch_add_i64(int64_t*, const int64_t*, int64_t, hipStream_t, int);
-void mv_launch_sgd(float*, const void*, void*, int, float, int64_t,
-                   hipStream_t, int);
-void mv_launch_sgd_f64(double*, const double*, double*, double, int64_t,
-                       hipStream_t, int);
-void mv_launch_momentum(float*, float*, const void*, void*, int, float,
-                        int64_t, hipStream_t, int);
-void mv_launch_momentum_f64(double*, double*, const double*, double, int64_t,
-                            hipStream_t, int);
-void mv_launch_adagrad(float*, float*, const void*, void*, int, float, float,
-                       float, int64_t, hipStream_t, int);
-void mv_launch_adagrad_f64(double*, double*, const double*, double, double,
-                           double, int64_t, hipStream_t, int);
-void mv_launch_dcasgd(float*, float*, const void*, void*, int, float, float,
-                      int64_t, hipStream_t, int);
-void mv_launch_dcasgda(float*, float*, float*, const void*, void*, int, float,
-                       float, float, float, int64_t, hipStream_t, int);
-// adam: (..., b1, b2, step = lr/(1-b1^t), rbc2 = 1/sqrt(1-b2^t),
-// decay = 1-lr*wd, eps, n), all scalars in double
-void mv_launch_adam(float*, float*, float*, const void*, void*, int, double,
-                    double, double, double, double, double, int64_t,
-                    hipStream_t, int);
-void mv_launch_adam_f64(double*, double*, double*, const double*, double,
-                        double, double, double, double, double, int64_t,
-                        hipStream_t, int);
-// keyed kernels: `vals` (the gather's `out`) is void* followed by `wire`
-void mv_launch_onebit_encode(const float*, float*, uint8_t*, int64_t,
-                             hipStream_t);
-void mv_launch_onebit_decode_sum(float*, const uint8_t*, int, int64_t,
-                                 hipStream_t);
-void mv_launch_row_gather(void*, int, const float*, const int64_t*, int64_t,
-                          int64_t, hipStream_t);
-void mv_launch_row_scatter_add(float*, const void*, int, const int64_t*, float,
-                               int64_t, int64_t, int, hipStream_t);
-void mv_launch_w2v(float*, float*, float*, float*, const int64_t*, const int*,
-                   const int64_t*, const float*, const int*, float, int64_t,
-                   int64_t, int, int, hipStream_t);
-void mv_launch_w2v_ns(float*, float*, float*, float*, const int64_t*,
-                      const int*, const int64_t*, const int64_t*, int64_t,
-                      int, uint64_t, float, int64_t, int64_t, int, int,
-                      hipStream_t);
-void mv_launch_lr_sigmoid_fwd(const float*, const int64_t*, const float*,
-                              const int*, const float*, const float*,
-                              float*, float*, int64_t, hipStream_t);
-void mv_launch_lr_sigmoid_scatter(float*, const int64_t*, const float*,
-                                  const int*, const float*, float, int,
-                                  float, int64_t, hipStream_t);
-void mv_launch_row_scatter_adagrad(float*, float*, const void*, int,
-                                   const int64_t*, float, float, float,
-                                   int64_t, int64_t, int, hipStream_t);
-// keyed stateful updaters: (shard, state..., vals, wire, rows, perm-or-null,
-// scalars..., nrows, cols)
-void mv_launch_row_momentum(float*, float*, const void*, int, const int64_t*,
-                            const int64_t*, float, int64_t, int64_t,
-                            hipStream_t);
-void mv_launch_row_dcasgd(float*, float*, const void*, int, const int64_t*,
-                          const int64_t*, float, float, int64_t, int64_t,
-                          hipStream_t);
-void mv_launch_row_dcasgda(float*, float*, float*, const void*, int,
-                           const int64_t*, const int64_t*, float, float,
-                           float, float, int64_t, int64_t, hipStream_t);
-void mv_launch_row_adam(float*, float*, float*, const void*, int,
-                        const int64_t*, const int64_t*, double, double,
-                        double, double, double, double, int64_t, int64_t,
-                        hipStream_t);
-void mv_launch_lr_softmax_fwd(const float*, const int64_t*, const float*,
-                              const int*, const float*, const float*,
-                              float*, float*, int64_t, int64_t, hipStream_t);
-void mv_launch_lr_softmax_scatter(float*, const int64_t*, const float*,
-                                  const int*, const float*, float, int,
-                                  float, int64_t, int64_t, hipStream_t);
-void mv_launch_lr_dense_post(float*, const float*, const float*, float*,
-                             float, int64_t, int64_t, hipStream_t);
-int mv_launch_lr_dense_fwd(const float*, const float*, const float*,
-                           const float*, float*, float*, float, int64_t,
-                           int64_t, int64_t, int, hipStream_t);
-void mv_launch_lr_ftrl_fwd(const float*, const int64_t*, const float*,
-                           const int*, const float*, const float*, float*,
-                           float*, float, float, float, float, int64_t,
-                           int64_t, hipStream_t);
-void mv_launch_lr_ftrl_scatter(float*, const int64_t*, const float*,
-                               const int*, const float*, float, float,
-                               float, float, int64_t, int64_t, hipStream_t);
-}
+#include "launchers.h"
 
 namespace {
 
@@ -614,6 +521,29 @@ int64_t check_csr(const torch::Tensor& keys, const torch::Tensor& vals,
   return ptr.numel() - 1;
 }
 
+// The optional per-sample weights of the logreg kernels: fp32, on the GPU,
+// contiguous, one per sample. Returns their pointer, or null without any.
+const float* opt_weights(const c10::optional<torch::Tensor>& wts, int64_t B) {
+  if (!wts.has_value()) return nullptr;
+  check_f32(*wts, "wts");
+  TORCH_CHECK(wts->numel() == B, "weights size mismatch");
+  return f32(*wts);
+}
+
+// K lies within the class counts the kernels are instantiated for, and the
+// table holds whole rows: K weights (softmax), 2*K state values (FTRL).
+void check_softmax_k(const torch::Tensor& w, int64_t K) {
+  TORCH_CHECK(K >= 2 && K <= 64,
+              "fused softmax supports 2..64 classes (got ", K, ")");
+  TORCH_CHECK(w.numel() % K == 0, "w must hold whole rows of K");
+}
+void check_ftrl_k(const torch::Tensor& zn, int64_t K) {
+  TORCH_CHECK(K >= 1 && K <= 32,
+              "fused FTRL supports 1..32 outputs (got ", K, ")");
+  TORCH_CHECK(zn.numel() % (2 * K) == 0,
+              "zn must hold whole rows of 2*K (z | n)");
+}
+
 void lr_sigmoid_forward(torch::Tensor w, torch::Tensor keys,
                         torch::Tensor vals, torch::Tensor ptr,
                         torch::Tensor labels,
@@ -624,16 +554,9 @@ void lr_sigmoid_forward(torch::Tensor w, torch::Tensor keys,
   int64_t B = check_csr(keys, vals, ptr);
   TORCH_CHECK(labels.numel() == B && err.numel() == B && loss.numel() == B,
               "batch size mismatch");
-  const float* wp = nullptr;
-  if (wts.has_value()) {
-    check_f32(*wts, "wts");
-    TORCH_CHECK(wts->numel() == B, "weights size mismatch");
-    wp = wts->data_ptr<float>();
-  }
-  mv_launch_lr_sigmoid_fwd(w.data_ptr<float>(), keys.data_ptr<int64_t>(),
-                           vals.data_ptr<float>(), ptr.data_ptr<int>(),
-                           labels.data_ptr<float>(), wp,
-                           err.data_ptr<float>(), loss.data_ptr<float>(), B,
+  mv_launch_lr_sigmoid_fwd(f32(w), keys.data_ptr<int64_t>(), f32(vals),
+                           ptr.data_ptr<int>(), f32(labels),
+                           opt_weights(wts, B), f32(err), f32(loss), B,
                            cur_stream());
 }
 
@@ -644,9 +567,8 @@ void lr_sigmoid_scatter(torch::Tensor w, torch::Tensor keys,
   check_f32(w, "w"); check_f32(vals, "vals"); check_f32(err, "err");
   int64_t B = check_csr(keys, vals, ptr);
   TORCH_CHECK(err.numel() == B, "err size mismatch");
-  mv_launch_lr_sigmoid_scatter(w.data_ptr<float>(), keys.data_ptr<int64_t>(),
-                               vals.data_ptr<float>(), ptr.data_ptr<int>(),
-                               err.data_ptr<float>(), (float)lr,
+  mv_launch_lr_sigmoid_scatter(f32(w), keys.data_ptr<int64_t>(), f32(vals),
+                               ptr.data_ptr<int>(), f32(err), (float)lr,
                                (int)reg_type, (float)reg_coef, B,
                                cur_stream());
 }
@@ -658,23 +580,14 @@ void lr_softmax_forward(torch::Tensor w, torch::Tensor keys,
                         torch::Tensor err, torch::Tensor loss, int64_t K) {
   check_f32(w, "w"); check_f32(vals, "vals"); check_f32(labels, "labels");
   check_f32(err, "err"); check_f32(loss, "loss");
-  TORCH_CHECK(K >= 2 && K <= 64,
-              "fused softmax supports 2..64 classes (got ", K, ")");
-  TORCH_CHECK(w.numel() % K == 0, "w must hold whole rows of K");
+  check_softmax_k(w, K);
   int64_t B = check_csr(keys, vals, ptr);
   TORCH_CHECK(labels.numel() == B && loss.numel() == B, "batch mismatch");
   TORCH_CHECK(err.numel() == B * K, "err must be [B, K]");
-  const float* wp = nullptr;
-  if (wts.has_value()) {
-    check_f32(*wts, "wts");
-    TORCH_CHECK(wts->numel() == B, "weights size mismatch");
-    wp = wts->data_ptr<float>();
-  }
-  mv_launch_lr_softmax_fwd(w.data_ptr<float>(), keys.data_ptr<int64_t>(),
-                           vals.data_ptr<float>(), ptr.data_ptr<int>(),
-                           labels.data_ptr<float>(), wp,
-                           err.data_ptr<float>(), loss.data_ptr<float>(),
-                           B, K, cur_stream());
+  mv_launch_lr_softmax_fwd(f32(w), keys.data_ptr<int64_t>(), f32(vals),
+                           ptr.data_ptr<int>(), f32(labels),
+                           opt_weights(wts, B), f32(err), f32(loss), B, K,
+                           cur_stream());
 }
 
 void lr_softmax_scatter(torch::Tensor w, torch::Tensor keys,
@@ -682,14 +595,11 @@ void lr_softmax_scatter(torch::Tensor w, torch::Tensor keys,
                         torch::Tensor err, double lr, int64_t reg_type,
                         double reg_coef, int64_t K) {
   check_f32(w, "w"); check_f32(vals, "vals"); check_f32(err, "err");
-  TORCH_CHECK(K >= 2 && K <= 64,
-              "fused softmax supports 2..64 classes (got ", K, ")");
-  TORCH_CHECK(w.numel() % K == 0, "w must hold whole rows of K");
+  check_softmax_k(w, K);
   int64_t B = check_csr(keys, vals, ptr);
   TORCH_CHECK(err.numel() == B * K, "err must be [B, K]");
-  mv_launch_lr_softmax_scatter(w.data_ptr<float>(), keys.data_ptr<int64_t>(),
-                               vals.data_ptr<float>(), ptr.data_ptr<int>(),
-                               err.data_ptr<float>(), (float)lr,
+  mv_launch_lr_softmax_scatter(f32(w), keys.data_ptr<int64_t>(), f32(vals),
+                               ptr.data_ptr<int>(), f32(err), (float)lr,
                                (int)reg_type, (float)reg_coef, B, K,
                                cur_stream());
 }
@@ -701,23 +611,13 @@ void lr_ftrl_forward(torch::Tensor zn, torch::Tensor keys,
                      double beta, double l1, double l2, int64_t K) {
   check_f32(zn, "zn"); check_f32(vals, "vals"); check_f32(labels, "labels");
   check_f32(err, "err"); check_f32(loss, "loss");
-  TORCH_CHECK(K >= 1 && K <= 32,
-              "fused FTRL supports 1..32 outputs (got ", K, ")");
-  TORCH_CHECK(zn.numel() % (2 * K) == 0,
-              "zn must hold whole rows of 2*K (z | n)");
+  check_ftrl_k(zn, K);
   int64_t B = check_csr(keys, vals, ptr);
   TORCH_CHECK(labels.numel() == B && loss.numel() == B, "batch mismatch");
   TORCH_CHECK(err.numel() == B * K, "err must be [B, K]");
-  const float* wp = nullptr;
-  if (wts.has_value()) {
-    check_f32(*wts, "wts");
-    TORCH_CHECK(wts->numel() == B, "weights size mismatch");
-    wp = wts->data_ptr<float>();
-  }
-  mv_launch_lr_ftrl_fwd(zn.data_ptr<float>(), keys.data_ptr<int64_t>(),
-                        vals.data_ptr<float>(), ptr.data_ptr<int>(),
-                        labels.data_ptr<float>(), wp, err.data_ptr<float>(),
-                        loss.data_ptr<float>(), (float)(1.0 / alpha),
+  mv_launch_lr_ftrl_fwd(f32(zn), keys.data_ptr<int64_t>(), f32(vals),
+                        ptr.data_ptr<int>(), f32(labels), opt_weights(wts, B),
+                        f32(err), f32(loss), (float)(1.0 / alpha),
                         (float)beta, (float)l1, (float)l2, B, K,
                         cur_stream());
 }
@@ -734,16 +634,8 @@ void lr_dense_post(torch::Tensor logits, torch::Tensor labels,
   TORCH_CHECK(K >= 1 && K <= 64,
               "fused dense post supports 1..64 classes (got ", K, ")");
   TORCH_CHECK(loss_acc.numel() == 1, "loss_acc must be a scalar");
-  const float* wp = nullptr;
-  if (wts.has_value()) {
-    check_f32(*wts, "wts");
-    TORCH_CHECK(wts->numel() == B, "weights size mismatch");
-    wp = wts->data_ptr<float>();
-  }
-  mv_launch_lr_dense_post(logits.data_ptr<float>(),
-                          labels.data_ptr<float>(), wp,
-                          loss_acc.data_ptr<float>(), (float)inv_b, B, K,
-                          cur_stream());
+  mv_launch_lr_dense_post(f32(logits), f32(labels), opt_weights(wts, B),
+                          f32(loss_acc), (float)inv_b, B, K, cur_stream());
 }
 
 bool lr_dense_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor labels,
@@ -759,36 +651,24 @@ bool lr_dense_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor labels,
   TORCH_CHECK(labels.numel() == B, "labels batch mismatch");
   TORCH_CHECK(diff.numel() == B * K, "diff must be [B, K]");
   TORCH_CHECK(loss_acc.numel() == 1, "loss_acc must be a scalar");
-  const float* wp = nullptr;
-  if (wts.has_value()) {
-    check_f32(*wts, "wts");
-    TORCH_CHECK(wts->numel() == B, "weights size mismatch");
-    wp = wts->data_ptr<float>();
-  }
-  return mv_launch_lr_dense_fwd(
-             x.data_ptr<float>(), w.data_ptr<float>(),
-             labels.data_ptr<float>(), wp, diff.data_ptr<float>(),
-             loss_acc.data_ptr<float>(), (float)inv_b, B, d, K,
-             nt ? 1 : 0, cur_stream()) != 0;
+  return mv_launch_lr_dense_fwd(f32(x), f32(w), f32(labels),
+                                opt_weights(wts, B), f32(diff), f32(loss_acc),
+                                (float)inv_b, B, d, K, nt ? 1 : 0,
+                                cur_stream()) != 0;
 }
-
 
 void lr_ftrl_scatter(torch::Tensor zn, torch::Tensor keys,
                      torch::Tensor vals, torch::Tensor ptr,
                      torch::Tensor err, double alpha, double beta, double l1,
                      double l2, int64_t K) {
   check_f32(zn, "zn"); check_f32(vals, "vals"); check_f32(err, "err");
-  TORCH_CHECK(K >= 1 && K <= 32,
-              "fused FTRL supports 1..32 outputs (got ", K, ")");
-  TORCH_CHECK(zn.numel() % (2 * K) == 0,
-              "zn must hold whole rows of 2*K (z | n)");
+  check_ftrl_k(zn, K);
   int64_t B = check_csr(keys, vals, ptr);
   TORCH_CHECK(err.numel() == B * K, "err must be [B, K]");
-  mv_launch_lr_ftrl_scatter(zn.data_ptr<float>(), keys.data_ptr<int64_t>(),
-                            vals.data_ptr<float>(), ptr.data_ptr<int>(),
-                            err.data_ptr<float>(), (float)(1.0 / alpha),
-                            (float)beta, (float)l1, (float)l2, B, K,
-                            cur_stream());
+  mv_launch_lr_ftrl_scatter(f32(zn), keys.data_ptr<int64_t>(), f32(vals),
+                            ptr.data_ptr<int>(), f32(err),
+                            (float)(1.0 / alpha), (float)beta, (float)l1,
+                            (float)l2, B, K, cur_stream());
 }
 
 }  // namespace

@@ -29,6 +29,8 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "launchers.h"
+
 #define WAVE 64
 #define BLOCK 256
 #define MAX_GRID 2048
@@ -1365,6 +1367,182 @@ extern "C" void mv_launch_w2v_ns(float* in_emb, float* out_emb,
 #undef W2V_CASE
 
 // ---------------------------------------------------------------------------
+// Logistic regression: eight kernels, one 64-lane wave per sample in all of
+// them, composed from the stages below. Each stage is written once; where
+// a term differs between objectives the kernel passes it in as a functor.
+// ---------------------------------------------------------------------------
+
+// keeps every log of a loss finite
+constexpr float LR_LOG_EPS = 1e-12f;
+
+// Wave-per-sample geometry: this wave's index in the grid, the lane's in
+// the wave, and the waves in the grid (the stride of the sample loop).
+// The kernel passes its blockDim.x in: read in here it costs every kernel a
+// vector load and a partial-block select in its prologue, which the
+// compiler folds away only where a kernel body reads it itself.
+struct Wave { int id, lane, n; };
+static __device__ __forceinline__ Wave this_wave(unsigned block) {
+  return {(int)((blockIdx.x * (int64_t)block + threadIdx.x) >> 6),
+          (int)(threadIdx.x & 63), (int)((gridDim.x * (int64_t)block) >> 6)};
+}
+
+// butterfly reductions: the result lands on every lane
+static __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int sh = 32; sh; sh >>= 1) v += __shfl_xor(v, sh, 64);
+  return v;
+}
+static __device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int sh = 32; sh; sh >>= 1) v = fmaxf(v, __shfl_xor(v, sh, 64));
+  return v;
+}
+template <int K>
+static __device__ __forceinline__ void wave_sum(float (&l)[K]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) l[k] = wave_sum(l[k]);
+}
+
+// l[lane] for the lanes below KK, `fill` for the rest: lane k owns class k
+// from here (the reduced logits are identical on all lanes). The unrolled
+// select keeps l[] in registers (no dynamic indexing).
+template <int K>
+static __device__ __forceinline__ float lane_select(const float (&l)[K],
+                                                    int lane, int KK,
+                                                    float fill) {
+  float mine = fill;
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    if (k < KK && lane == k) mine = l[k];
+  return mine;
+}
+
+// One feature of a sample's CSR walk: l[k] += v * term(row, k) for the KK
+// classes, `row` being the feature's table row and v its value. The
+// `k < KK` guards fold away where the kernel pins KK at compile time (see
+// k_lr_softmax_fwd). The lane-strided loop around it stays in the two
+// kernels: moved into a function with it (l by reference or returned by
+// value) it was scheduled differently, 90 VGPRs for 61 in
+// k_lr_softmax_fwd<32> and 97 for 86 in k_lr_ftrl_fwd<32>, an occupancy
+// step each (profiles/lr_refactor.md).
+template <int K, class Term>
+static __device__ __forceinline__ void add_feature(float (&l)[K], float v,
+                                                   const float* row, int KK,
+                                                   Term term) {
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    if (k < KK) l[k] += v * term(row, k);
+}
+
+// sample i's weight; 1 where the batch carries none
+static __device__ __forceinline__ float weight_of(const float* wts, int i) {
+  return wts ? wts[i] : 1.f;
+}
+
+// Softmax of sample i across the live lanes of a wave, lane k holding class
+// k's logit in `mine` (dead lanes hold -1e30f). Writes this lane's
+// (p_k - [k == y]) * wt to out[lane] and returns the sample's loss
+// -log(p_y + eps) (SoftmaxObjective.loss) on every lane. Label and weight
+// are read here, after the reductions: read before them they stay live
+// across them (87 VGPRs for 61 in k_lr_softmax_fwd<32>).
+static __device__ __forceinline__ float softmax_epilogue(
+    float mine, bool live, int lane, int i, const float* labels,
+    const float* wts, float* out) {
+  float mx = wave_max(mine);
+  float e = live ? expf(mine - mx) : 0.f;
+  float se = wave_sum(e);
+  float p = e / se;
+  int y = (int)labels[i];
+  float wt = weight_of(wts, i);
+  if (live) out[lane] = (p - (lane == y)) * wt;
+  float py = __shfl(p, y, 64);
+  return -logf(py + LR_LOG_EPS);
+}
+
+// Sigmoid of one logit s of sample i against its target y: the label itself
+// for a binary output (cls < 0), else [cls == label]. Writes (p - y) * wt to
+// *err and returns the binary loss -(y log p + (1-y) log(1-p))
+// (Objective.loss). Label and weight are read after p, as in
+// softmax_epilogue.
+static __device__ __forceinline__ float sigmoid_epilogue(
+    float s, int cls, int i, const float* labels, const float* wts,
+    float* err) {
+  float p = 1.f / (1.f + expf(-s));
+  float y = (cls < 0) ? labels[i] : (float)(cls == (int)labels[i]);
+  float wt = weight_of(wts, i);
+  *err = (p - y) * wt;
+  return -(y * logf(p + LR_LOG_EPS) + (1.f - y) * logf(1.f - p + LR_LOG_EPS));
+}
+
+// g plus the regulariser's gradient at the weight *w: reg_type 0 none,
+// 1 = l1 coef*sign(w), 2 = l2 coef*w. The weight is read only if needed.
+static __device__ __forceinline__ float with_reg(float g, const float* w,
+                                                 int reg_type, float coef) {
+  if (reg_type == 1) {
+    float wv = *w;
+    g += coef * ((wv > 0.f) - (wv < 0.f));
+  } else if (reg_type == 2) {
+    g += coef * *w;
+  }
+  return g;
+}
+
+// f(j, k) over the flattened (feature, class) pairs of one sample: lane t
+// handles pair t, t+64, ... -> consecutive lanes hit consecutive classes of
+// the same table row (coalesced atomics).
+template <class F>
+static __device__ __forceinline__ void for_pairs(int jb, int je, int K,
+                                                 int lane, F f) {
+  // u32 pair math: nnz*K < 2^32 always (B*nnz is int32 CSR already);
+  // a 64-bit div per pair was ~40 VALU cycles each
+  uint32_t pairs = (uint32_t)(je - jb) * (uint32_t)K;
+  for (uint32_t t = lane; t < pairs; t += 64) {
+    uint32_t q = t / (uint32_t)K;
+    f(jb + (int)q, (int)(t - q * (uint32_t)K));
+  }
+}
+
+// Block mean-loss accumulate, in two halves around a kernel's sample loop:
+// *loss_acc += inv_b * (the sum of every wave's lane-0 ll_sum). The barrier
+// of the first half also publishes what the kernel wrote to LDS before it.
+// Loss goes lane-private -> one LDS atomic per wave -> ONE global
+// atomic per block: a naive per-sample atomicAdd on the single
+// loss_acc cache line serialized 4096 waves and cost 54 us (measured,
+// profiles/round2_dense_fused.md) — 13x the kernel's real work.
+// (One function taking the loop as a lambda cost k_lr_dense_post 3 VGPRs
+// and 0.3 us at K = 1, profiles/lr_refactor.md.)
+static __device__ __forceinline__ float* block_loss_begin() {
+  __shared__ float block_loss;
+  if (threadIdx.x == 0) block_loss = 0.f;
+  __syncthreads();
+  return &block_loss;
+}
+static __device__ __forceinline__ void block_loss_end(float* block_loss,
+                                                      float* loss_acc,
+                                                      float inv_b, int lane,
+                                                      float ll_sum) {
+  if (lane == 0 && ll_sum != 0.f) atomicAdd(block_loss, ll_sum);
+  __syncthreads();
+  if (threadIdx.x == 0 && *block_loss != 0.f)
+    atomicAdd(loss_acc, *block_loss * inv_b);
+}
+
+// f(kint<K>()) for a runtime K in [LO, HI], so that f can instantiate a
+// kernel on the exact class count; false, and no call, for any other K.
+template <int N> using kint = std::integral_constant<int, N>;
+template <int LO, int HI, class F>
+static bool with_exact_k(int64_t K, F f) {
+  if constexpr (LO <= HI) {
+    if (K == LO) {
+      f(kint<LO>());
+      return true;
+    }
+    return with_exact_k<LO + 1, HI>(K, f);
+  }
+  return false;
+}
+
+// ---------------------------------------------------------------------------
 // Fused sparse logistic regression minibatch (K13/K14 fused): the
 // reference's per-sample scalar loops (LogisticRegression
 // objective/objective.cpp:63-188 sigmoid path + updater apply) as TWO
@@ -1375,7 +1553,7 @@ extern "C" void mv_launch_w2v_ns(float* in_emb, float* out_emb,
 // reduces, then err[i] = (sigmoid(s) - y_i) * wt_i and the log loss.
 // Scatter: same geometry; lanes apply w[keys_j] -= lr * (vals_j * err_i
 // + reg(w)) with device atomics (duplicate keys accumulate, matching
-// index_add semantics). reg: 0 none, 1 = l1 coef*sign(w), 2 = l2 coef*w.
+// index_add semantics).
 // ---------------------------------------------------------------------------
 
 __global__ void k_lr_sigmoid_fwd(const float* __restrict__ w,
@@ -1386,24 +1564,14 @@ __global__ void k_lr_sigmoid_fwd(const float* __restrict__ w,
                                  const float* __restrict__ wts,
                                  float* __restrict__ err,
                                  float* __restrict__ loss, int B) {
-  int wid = (int)((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6);
-  int lane = threadIdx.x & 63;
-  int nwaves = (int)((gridDim.x * (int64_t)blockDim.x) >> 6);
-  for (int i = wid; i < B; i += nwaves) {
+  const Wave wv = this_wave(blockDim.x);
+  for (int i = wv.id; i < B; i += wv.n) {
     int jb = ptr[i], je = ptr[i + 1];
     float s = 0.f;
-    for (int j = jb + lane; j < je; j += 64) s += vals[j] * w[keys[j]];
-#pragma unroll
-    for (int sh = 32; sh; sh >>= 1) s += __shfl_xor(s, sh, 64);
-    if (lane == 0) {
-      float p = 1.f / (1.f + expf(-s));
-      float y = labels[i];
-      float e = p - y;
-      if (wts) e *= wts[i];
-      err[i] = e;
-      const float eps = 1e-12f;
-      loss[i] = -(y * logf(p + eps) + (1.f - y) * logf(1.f - p + eps));
-    }
+    for (int j = jb + wv.lane; j < je; j += 64) s += vals[j] * w[keys[j]];
+    s = wave_sum(s);
+    if (wv.lane == 0)
+      loss[i] = sigmoid_epilogue(s, -1, i, labels, wts, &err[i]);
   }
 }
 
@@ -1414,22 +1582,13 @@ __global__ void k_lr_sigmoid_scatter(float* __restrict__ w,
                                      const float* __restrict__ err,
                                      float lr, int reg_type, float reg_coef,
                                      int B) {
-  int wid = (int)((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6);
-  int lane = threadIdx.x & 63;
-  int nwaves = (int)((gridDim.x * (int64_t)blockDim.x) >> 6);
-  for (int i = wid; i < B; i += nwaves) {
+  const Wave wv = this_wave(blockDim.x);
+  for (int i = wv.id; i < B; i += wv.n) {
     int jb = ptr[i], je = ptr[i + 1];
     float e = err[i];
-    for (int j = jb + lane; j < je; j += 64) {
-      int64_t k = keys[j];
-      float g = vals[j] * e;
-      if (reg_type == 1) {
-        float wv = w[k];
-        g += reg_coef * ((wv > 0.f) - (wv < 0.f));
-      } else if (reg_type == 2) {
-        g += reg_coef * w[k];
-      }
-      atomicAdd(&w[k], -lr * g);
+    for (int j = jb + wv.lane; j < je; j += 64) {
+      float* wk = w + keys[j];
+      atomicAdd(wk, -lr * with_reg(vals[j] * e, wk, reg_type, reg_coef));
     }
   }
 }
@@ -1487,44 +1646,18 @@ __global__ void k_lr_softmax_fwd(const float* __restrict__ w,
                                  float* __restrict__ err,
                                  float* __restrict__ loss, int B, int KK) {
   if (KKC != 0) KK = KKC;
-  int wid = (int)((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6);
-  int lane = threadIdx.x & 63;
-  int nwaves = (int)((gridDim.x * (int64_t)blockDim.x) >> 6);
-  for (int i = wid; i < B; i += nwaves) {
+  const Wave wv = this_wave(blockDim.x);
+  for (int i = wv.id; i < B; i += wv.n) {
     int jb = ptr[i], je = ptr[i + 1];
-    float l[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) l[k] = 0.f;
-    for (int j = jb + lane; j < je; j += 64) {
-      float v = vals[j];
-      const float* row = w + keys[j] * KK;
-#pragma unroll
-      for (int k = 0; k < K; ++k)
-        if (k < KK) l[k] += v * row[k];
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-#pragma unroll
-      for (int sh = 32; sh; sh >>= 1) l[k] += __shfl_xor(l[k], sh, 64);
-    // lane k owns class k from here (logits identical on all lanes);
-    // unrolled select keeps l[] in registers (no dynamic indexing)
-    float mine = -1e30f;
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-      if (k < KK && lane == k) mine = l[k];
-    float mx = mine;
-#pragma unroll
-    for (int sh = 32; sh; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
-    float e = (lane < KK) ? expf(mine - mx) : 0.f;
-    float se = e;
-#pragma unroll
-    for (int sh = 32; sh; sh >>= 1) se += __shfl_xor(se, sh, 64);
-    float p = e / se;
-    int y = (int)labels[i];
-    float wt = wts ? wts[i] : 1.f;
-    if (lane < KK) err[(int64_t)i * KK + lane] = (p - (lane == y)) * wt;
-    float py = __shfl(p, y, 64);
-    if (lane == 0) loss[i] = -logf(py + 1e-12f);
+    float l[K] = {};
+    for (int j = jb + wv.lane; j < je; j += 64)
+      add_feature(l, vals[j], w + keys[j] * KK, KK,
+                  [](const float* row, int k) { return row[k]; });
+    wave_sum(l);
+    float ll = softmax_epilogue(lane_select(l, wv.lane, KK, -1e30f),
+                                wv.lane < KK, wv.lane, i, labels, wts,
+                                err + (int64_t)i * KK);
+    if (wv.lane == 0) loss[i] = ll;
   }
 }
 
@@ -1535,32 +1668,13 @@ __global__ void k_lr_softmax_scatter(float* __restrict__ w,
                                      const float* __restrict__ err,
                                      float lr, int reg_type, float reg_coef,
                                      int B, int K) {
-  // flattened (feature, class) pairs per sample: lane t handles pair
-  // t, t+64, ... -> consecutive lanes hit consecutive classes of the
-  // same w row (coalesced atomics)
-  int wid = (int)((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6);
-  int lane = threadIdx.x & 63;
-  int nwaves = (int)((gridDim.x * (int64_t)blockDim.x) >> 6);
-  for (int i = wid; i < B; i += nwaves) {
-    int jb = ptr[i], je = ptr[i + 1];
-    // u32 pair math: nnz*K < 2^32 always (B*nnz is int32 CSR already);
-    // a 64-bit div per pair was ~40 VALU cycles each
-    uint32_t pairs = (uint32_t)(je - jb) * (uint32_t)K;
+  const Wave wv = this_wave(blockDim.x);
+  for (int i = wv.id; i < B; i += wv.n) {
     const float* e = err + (int64_t)i * K;
-    for (uint32_t t = lane; t < pairs; t += 64) {
-      uint32_t q = t / (uint32_t)K;
-      int j = jb + (int)q;
-      int k = (int)(t - q * (uint32_t)K);
-      int64_t idx = keys[j] * K + k;
-      float g = vals[j] * e[k];
-      if (reg_type == 1) {
-        float wv = w[idx];
-        g += reg_coef * ((wv > 0.f) - (wv < 0.f));
-      } else if (reg_type == 2) {
-        g += reg_coef * w[idx];
-      }
-      atomicAdd(&w[idx], -lr * g);
-    }
+    for_pairs(ptr[i], ptr[i + 1], K, wv.lane, [&](int j, int k) {
+      float* wk = w + (keys[j] * K + k);
+      atomicAdd(wk, -lr * with_reg(vals[j] * e[k], wk, reg_type, reg_coef));
+    });
   }
 }
 
@@ -1570,23 +1684,15 @@ extern "C" void mv_launch_lr_softmax_fwd(
     int64_t B, int64_t K, hipStream_t s) {
   if (!B) return;
   int grid = grid_for(B * 64);
-#define SMAX_ARGS w, keys, vals, ptr, labels, wts, err, loss, (int)B, (int)K
-#define SMAX_EXACT(KC)                                                       \
-  case KC:                                                                   \
-    k_lr_softmax_fwd<KC, KC><<<grid, BLOCK, 0, s>>>(SMAX_ARGS);              \
-    return
-  switch (K) {
-    SMAX_EXACT(2); SMAX_EXACT(3); SMAX_EXACT(4); SMAX_EXACT(5);
-    SMAX_EXACT(6); SMAX_EXACT(7); SMAX_EXACT(8); SMAX_EXACT(9);
-    SMAX_EXACT(10); SMAX_EXACT(11); SMAX_EXACT(12); SMAX_EXACT(13);
-    SMAX_EXACT(14); SMAX_EXACT(15); SMAX_EXACT(16);
-    default: break;
-  }
-  if (K <= 32) k_lr_softmax_fwd<32><<<grid, BLOCK, 0, s>>>(SMAX_ARGS);
-  else if (K <= 64) k_lr_softmax_fwd<64><<<grid, BLOCK, 0, s>>>(SMAX_ARGS);
+  auto launch = [&](auto kb, auto kkc) {
+    k_lr_softmax_fwd<decltype(kb)::value, decltype(kkc)::value>
+        <<<grid, BLOCK, 0, s>>>(w, keys, vals, ptr, labels, wts, err, loss,
+                                (int)B, (int)K);
+  };
+  if (with_exact_k<2, 16>(K, [&](auto k) { launch(k, k); })) return;
+  if (K <= 32) launch(kint<32>(), kint<0>());
+  else if (K <= 64) launch(kint<64>(), kint<0>());
   else __builtin_trap();  // K > 64: host refuses before launch
-#undef SMAX_EXACT
-#undef SMAX_ARGS
 }
 
 extern "C" void mv_launch_lr_softmax_scatter(
@@ -1635,45 +1741,39 @@ __global__ void k_lr_ftrl_fwd(const float* __restrict__ zn,
                               float alpha_inv, float beta, float l1,
                               float l2, int B, int KK) {
   if (KKC != 0) KK = KKC;  // see k_lr_softmax_fwd: exact-K folds guards
-  int wid = (int)((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6);
-  int lane = threadIdx.x & 63;
-  int nwaves = (int)((gridDim.x * (int64_t)blockDim.x) >> 6);
-  for (int i = wid; i < B; i += nwaves) {
+  const Wave wv = this_wave(blockDim.x);
+  for (int i = wv.id; i < B; i += wv.n) {
     int jb = ptr[i], je = ptr[i + 1];
-    float l[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) l[k] = 0.f;
-    for (int j = jb + lane; j < je; j += 64) {
-      float v = vals[j];
-      const float* row = zn + keys[j] * (2 * KK);
-#pragma unroll
-      for (int k = 0; k < K; ++k)
-        if (k < KK)
-          l[k] += v * ftrl_w(row[k], row[KK + k], alpha_inv, beta, l1, l2);
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-#pragma unroll
-      for (int sh = 32; sh; sh >>= 1) l[k] += __shfl_xor(l[k], sh, 64);
+    float l[K] = {};
+    for (int j = jb + wv.lane; j < je; j += 64)
+      add_feature(l, vals[j], zn + keys[j] * (2 * KK), KK,
+                  [&](const float* row, int k) {
+                    return ftrl_w(row[k], row[KK + k], alpha_inv, beta, l1,
+                                  l2);
+                  });
+    wave_sum(l);
     float ll = 0.f;
-    if (lane < KK) {
-      float mine = 0.f;
-#pragma unroll
-      for (int k = 0; k < K; ++k)
-        if (lane == k) mine = l[k];
+    if (wv.lane < KK) {
+      // sigmoid_epilogue (the formula of record) written out: through the
+      // call k_lr_ftrl_fwd<2,2> ran 0.4 us (5 %) over the parent's slowest
+      // repeat; this form compiles to the code it had before the helpers
+      // (profiles/lr_refactor.md). Every lane in here is below KK <= K, so
+      // the select needs no guard.
+      float mine = lane_select(l, wv.lane, K, 0.f);
       float p = 1.f / (1.f + expf(-mine));
       int y = (int)labels[i];
-      float yk = (KK == 1) ? labels[i] : (float)(lane == y);
-      float wt = wts ? wts[i] : 1.f;
-      err[(int64_t)i * KK + lane] = (p - yk) * wt;
-      ll = -(yk * logf(p + 1e-12f) + (1.f - yk) * logf(1.f - p + 1e-12f));
+      float yk = (KK == 1) ? labels[i] : (float)(wv.lane == y);
+      float wt = weight_of(wts, i);
+      err[(int64_t)i * KK + wv.lane] = (p - yk) * wt;
+      ll = -(yk * logf(p + LR_LOG_EPS) +
+             (1.f - yk) * logf(1.f - p + LR_LOG_EPS));
     }
     // binary NLL summed over the KK outputs, as Objective.loss does: lanes
     // >= KK hold 0 and KK <= K, so the shifts below K bring every term to
     // lane 0 (none at K == 1)
     for (int sh = 32; sh; sh >>= 1)
       if (sh < K) ll += __shfl_xor(ll, sh, 64);
-    if (lane == 0) loss[i] = ll;
+    if (wv.lane == 0) loss[i] = ll;
   }
 }
 
@@ -1684,17 +1784,10 @@ __global__ void k_lr_ftrl_scatter(float* __restrict__ zn,
                                   const float* __restrict__ err,
                                   float alpha_inv, float beta, float l1,
                                   float l2, int B, int K) {
-  int wid = (int)((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6);
-  int lane = threadIdx.x & 63;
-  int nwaves = (int)((gridDim.x * (int64_t)blockDim.x) >> 6);
-  for (int i = wid; i < B; i += nwaves) {
-    int jb = ptr[i], je = ptr[i + 1];
-    uint32_t pairs = (uint32_t)(je - jb) * (uint32_t)K;  // see softmax scatter
+  const Wave wv = this_wave(blockDim.x);
+  for (int i = wv.id; i < B; i += wv.n) {
     const float* e = err + (int64_t)i * K;
-    for (uint32_t t = lane; t < pairs; t += 64) {
-      uint32_t q = t / (uint32_t)K;
-      int j = jb + (int)q;
-      int k = (int)(t - q * (uint32_t)K);
+    for_pairs(ptr[i], ptr[i + 1], K, wv.lane, [&](int j, int k) {
       int64_t base = keys[j] * (2 * (int64_t)K);
       float z = zn[base + k];
       float n = zn[base + K + k];
@@ -1706,7 +1799,7 @@ __global__ void k_lr_ftrl_scatter(float* __restrict__ zn,
       // local state -= (dz | dn): z -= dz, n -= -g2
       zn[base + k] = z - dz;
       zn[base + K + k] = n + g2;
-    }
+    });
   }
 }
 
@@ -1717,23 +1810,14 @@ extern "C" void mv_launch_lr_ftrl_fwd(
     hipStream_t s) {
   if (!B) return;
   int grid = grid_for(B * 64);
-#define FTRL_ARGS zn, keys, vals, ptr, labels, wts, err, loss, alpha_inv, \
-                  beta, l1, l2, (int)B, (int)K
-#define FTRL_EXACT(KC)                                                       \
-  case KC:                                                                   \
-    k_lr_ftrl_fwd<KC, KC><<<grid, BLOCK, 0, s>>>(FTRL_ARGS);                 \
-    return
-  switch (K) {
-    FTRL_EXACT(1); FTRL_EXACT(2); FTRL_EXACT(3); FTRL_EXACT(4);
-    FTRL_EXACT(5); FTRL_EXACT(6); FTRL_EXACT(7); FTRL_EXACT(8);
-    FTRL_EXACT(9); FTRL_EXACT(10); FTRL_EXACT(11); FTRL_EXACT(12);
-    FTRL_EXACT(13); FTRL_EXACT(14); FTRL_EXACT(15); FTRL_EXACT(16);
-    default: break;
-  }
-  if (K <= 32) k_lr_ftrl_fwd<32><<<grid, BLOCK, 0, s>>>(FTRL_ARGS);
+  auto launch = [&](auto kb, auto kkc) {
+    k_lr_ftrl_fwd<decltype(kb)::value, decltype(kkc)::value>
+        <<<grid, BLOCK, 0, s>>>(zn, keys, vals, ptr, labels, wts, err, loss,
+                                alpha_inv, beta, l1, l2, (int)B, (int)K);
+  };
+  if (with_exact_k<1, 16>(K, [&](auto k) { launch(k, k); })) return;
+  if (K <= 32) launch(kint<32>(), kint<0>());
   else __builtin_trap();  // K > 32: host refuses before launch
-#undef FTRL_EXACT
-#undef FTRL_ARGS
 }
 
 extern "C" void mv_launch_lr_ftrl_scatter(
@@ -1760,53 +1844,53 @@ extern "C" void mv_launch_lr_ftrl_scatter(
 // loss = -(y log p + (1-y) log(1-p)) (base Objective.loss at O=1).
 // ---------------------------------------------------------------------------
 
+// Sample i of the dense kernels, lane k holding class k's logit in `mine`:
+// writes the K diffs to out[0..K) and returns the sample's loss on lane 0,
+// 0 on the others.
+static __device__ __forceinline__ float dense_sample(
+    float mine, int K, int lane, int i, const float* labels,
+    const float* wts, float* out) {
+  float ll = 0.f;
+  if (K == 1) {
+    if (lane == 0) ll = sigmoid_epilogue(mine, -1, i, labels, wts, out);
+  } else {
+    float t = softmax_epilogue(mine, lane < K, lane, i, labels, wts, out);
+    if (lane == 0) ll = t;
+  }
+  return ll;
+}
+
 __global__ void k_lr_dense_post(float* __restrict__ logits,
                                 const float* __restrict__ labels,
                                 const float* __restrict__ wts,
                                 float* __restrict__ loss_acc,
                                 float inv_b, int B, int K) {
-  // Loss goes lane-private -> one LDS atomic per wave -> ONE global
-  // atomic per block: a naive per-sample atomicAdd on the single
-  // loss_acc cache line serialized 4096 waves and cost 54 us (measured,
-  // profiles/round2_dense_fused.md) — 13x the kernel's real work.
-  __shared__ float block_loss;
-  if (threadIdx.x == 0) block_loss = 0.f;
-  __syncthreads();
-  int wid = (int)((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6);
-  int lane = threadIdx.x & 63;
-  int nwaves = (int)((gridDim.x * (int64_t)blockDim.x) >> 6);
-  const float eps = 1e-12f;
+  float* block_loss = block_loss_begin();
+  const Wave wv = this_wave(blockDim.x);
+  const int lane = wv.lane;
   float ll_sum = 0.f;
-  for (int i = wid; i < B; i += nwaves) {
-    float wt = wts ? wts[i] : 1.f;
+  for (int i = wv.id; i < B; i += wv.n) {
     if (K == 1) {
+      // sigmoid_epilogue (the formula of record) written out: through the
+      // call this path ran 0.3 us (3 %) over the parent's slowest repeat
+      // (profiles/lr_refactor.md)
       if (lane == 0) {
+        float wt = weight_of(wts, i);
         float s = logits[i];
         float p = 1.f / (1.f + expf(-s));
         float y = labels[i];
         logits[i] = (p - y) * wt;
-        ll_sum -= y * logf(p + eps) + (1.f - y) * logf(1.f - p + eps);
+        ll_sum -= y * logf(p + LR_LOG_EPS) +
+                  (1.f - y) * logf(1.f - p + LR_LOG_EPS);
       }
       continue;
     }
-    float l = (lane < K) ? logits[(int64_t)i * K + lane] : -1e30f;
-    float mx = l;
-#pragma unroll
-    for (int sh = 32; sh; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
-    float e = (lane < K) ? expf(l - mx) : 0.f;
-    float se = e;
-#pragma unroll
-    for (int sh = 32; sh; sh >>= 1) se += __shfl_xor(se, sh, 64);
-    float p = e / se;
-    int y = (int)labels[i];
-    if (lane < K) logits[(int64_t)i * K + lane] = (p - (lane == y)) * wt;
-    float py = __shfl(p, y, 64);
-    if (lane == 0) ll_sum -= logf(py + eps);
+    float* row = logits + (int64_t)i * K;
+    float t = softmax_epilogue((lane < K) ? row[lane] : -1e30f, lane < K,
+                               lane, i, labels, wts, row);
+    if (lane == 0) ll_sum += t;
   }
-  if (lane == 0 && ll_sum != 0.f) atomicAdd(&block_loss, ll_sum);
-  __syncthreads();
-  if (threadIdx.x == 0 && block_loss != 0.f)
-    atomicAdd(loss_acc, block_loss * inv_b);
+  block_loss_end(block_loss, loss_acc, inv_b, lane, ll_sum);
 }
 
 extern "C" void mv_launch_lr_dense_post(float* logits, const float* labels,
@@ -1846,66 +1930,25 @@ __global__ void k_lr_dense_fwd(const float* __restrict__ X,
                                float* __restrict__ loss_acc,
                                float inv_b, int B, int d) {
   extern __shared__ float wlds[];  // [d][K|1]
-  __shared__ float block_loss;
   constexpr int S = K | 1;  // odd stride: (S*lane) % 64 banks all distinct
   for (int t = threadIdx.x; t < d * K; t += blockDim.x)
     wlds[(t / K) * S + (t % K)] = W[t];
-  if (threadIdx.x == 0) block_loss = 0.f;
-  __syncthreads();
-
-  int wid = (int)((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6);
-  int lane = threadIdx.x & 63;
-  int nwaves = (int)((gridDim.x * (int64_t)blockDim.x) >> 6);
-  const float eps = 1e-12f;
+  float* block_loss = block_loss_begin();  // its barrier publishes wlds
+  const Wave wv = this_wave(blockDim.x);
   float ll_sum = 0.f;
-  for (int i = wid; i < B; i += nwaves) {
+  for (int i = wv.id; i < B; i += wv.n) {
     const float* __restrict__ xrow = X + (int64_t)i * d;
-    float acc[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = 0.f;
-    for (int e = lane; e < d; e += 64) {
+    float acc[K] = {};
+    for (int e = wv.lane; e < d; e += 64) {
       float x = NT ? __builtin_nontemporal_load(xrow + e) : xrow[e];
-      const float* wr = wlds + e * S;
-#pragma unroll
-      for (int k = 0; k < K; ++k) acc[k] += x * wr[k];
+      add_feature(acc, x, wlds + e * S, K,
+                  [](const float* wr, int k) { return wr[k]; });
     }
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-#pragma unroll
-      for (int sh = 32; sh; sh >>= 1) acc[k] += __shfl_xor(acc[k], sh, 64);
-    float wt = wts ? wts[i] : 1.f;
-    if (K == 1) {
-      if (lane == 0) {
-        float p = 1.f / (1.f + expf(-acc[0]));
-        float y = labels[i];
-        diff[i] = (p - y) * wt;
-        ll_sum -= y * logf(p + eps) + (1.f - y) * logf(1.f - p + eps);
-      }
-      continue;
-    }
-    // lane k owns class k (logits identical on all lanes after the
-    // reductions); unrolled select keeps acc[] in registers
-    float mine = -1e30f;
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-      if (lane == k) mine = acc[k];
-    float mx = mine;
-#pragma unroll
-    for (int sh = 32; sh; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
-    float e = (lane < K) ? expf(mine - mx) : 0.f;
-    float se = e;
-#pragma unroll
-    for (int sh = 32; sh; sh >>= 1) se += __shfl_xor(se, sh, 64);
-    float p = e / se;
-    int y = (int)labels[i];
-    if (lane < K) diff[(int64_t)i * K + lane] = (p - (lane == y)) * wt;
-    float py = __shfl(p, y, 64);
-    if (lane == 0) ll_sum -= logf(py + eps);
+    wave_sum(acc);
+    ll_sum += dense_sample(lane_select(acc, wv.lane, K, -1e30f), K, wv.lane,
+                           i, labels, wts, diff + (int64_t)i * K);
   }
-  if (lane == 0 && ll_sum != 0.f) atomicAdd(&block_loss, ll_sum);
-  __syncthreads();
-  if (threadIdx.x == 0 && block_loss != 0.f)
-    atomicAdd(loss_acc, block_loss * inv_b);
+  block_loss_end(block_loss, loss_acc, inv_b, wv.lane, ll_sum);
 }
 
 extern "C" int mv_launch_lr_dense_fwd(const float* X, const float* W,
@@ -1922,23 +1965,11 @@ extern "C" int mv_launch_lr_dense_fwd(const float* X, const float* W,
   int64_t blocks = (B + 15) / 16;  // 16 waves/block, one sample per wave
   if (blocks > 256) blocks = 256;  // 1 LDS-heavy WG per CU
   int grid = (int)blocks;
-  switch (K) {
-#define LAUNCH_KT(KT)                                                      \
-  case KT:                                                                 \
-    if (nt)                                                                \
-      k_lr_dense_fwd<KT, true><<<grid, COPY_BLOCK, lds, s>>>(              \
-          X, W, labels, wts, diff, loss_acc, inv_b, (int)B, (int)d);       \
-    else                                                                   \
-      k_lr_dense_fwd<KT, false><<<grid, COPY_BLOCK, lds, s>>>(             \
-          X, W, labels, wts, diff, loss_acc, inv_b, (int)B, (int)d);       \
-    break
-    LAUNCH_KT(1); LAUNCH_KT(2); LAUNCH_KT(3); LAUNCH_KT(4);
-    LAUNCH_KT(5); LAUNCH_KT(6); LAUNCH_KT(7); LAUNCH_KT(8);
-    LAUNCH_KT(9); LAUNCH_KT(10); LAUNCH_KT(11); LAUNCH_KT(12);
-    LAUNCH_KT(13); LAUNCH_KT(14); LAUNCH_KT(15); LAUNCH_KT(16);
-#undef LAUNCH_KT
-    default: return 0;
-  }
-  return 1;
+  return with_exact_k<1, 16>(K, [&](auto k) {
+    constexpr int KT = decltype(k)::value;
+    auto* kernel = nt ? k_lr_dense_fwd<KT, true> : k_lr_dense_fwd<KT, false>;
+    kernel<<<grid, COPY_BLOCK, lds, s>>>(X, W, labels, wts, diff, loss_acc,
+                                         inv_b, (int)B, (int)d);
+  });
 }
 
