@@ -78,12 +78,13 @@ def build_app(table, words, dim):
     @app.get("/nn/{word}")
     def nn(word: str, k: int = 5):
         q = vec_of(word)
-        full = table.get()                      # all-gather of shards
-        sims = torch.nn.functional.cosine_similarity(
-            full, q.unsqueeze(0), dim=1)
-        top = torch.topk(sims, min(k + 1, len(words)))
+        # each owner scans its own shard and sends back its best rows; the
+        # table never leaves the servers. One extra for the word itself.
+        # nearest_rows serves at most 64 rows per query.
+        want = max(1, min(k + 1, len(words), 64))
+        scores, ids = table.nearest_rows(q, want)
         out = [{"word": words[int(i)], "score": float(s)}
-               for s, i in zip(top.values, top.indices)
+               for s, i in zip(scores[0].cpu(), ids[0].cpu())
                if words[int(i)] != word][:k]
         return {"word": word, "neighbors": out}
 

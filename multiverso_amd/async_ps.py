@@ -58,6 +58,10 @@ OP_FLUSH = 7        # fence: ack after all my prior requests are applied
 OP_FINISH = 8       # worker is done (Zoo StopPS / FinishTrain parity)
 OP_GET_STALE = 9    # sparse table: rows stale FOR THIS WORKER; reply =
                     # count + global ids + values (matrix.cpp:478,540)
+OP_NEAREST = 10     # nearest_rows: payload = Q fp32 queries of num_col;
+                    # reply = one blob, Q*k int64 global ids then Q*k fp32
+                    # scores. Header: n_keys = Q, n_vals = k, has_opt = 1
+                    # for cosine and 0 for dot (the request has no option)
 
 _HDR = 6  # int64 fields: [op, table_id, n_keys, n_vals, want_ack, has_opt]
 
@@ -292,6 +296,51 @@ class AsyncEngine:
             out[rows] = buf.view(-1, unit).to(table.device)
         return out
 
+    def nearest(self, table, q: torch.Tensor, k: int, metric: str):
+        """nearest_rows: every server selects its k best rows per query on
+        arrival; returns the candidates, ``(scores, ids)`` each ``[Q, n*k]``,
+        for the caller to merge. The reply's size is known here, so its recv
+        is posted at send time; the local shard is served without the
+        transport."""
+        zoo = self.zoo
+        nq = q.shape[0]
+        cosine = 1 if metric == "cosine" else 0
+        q_cpu = None
+        works: List = []
+        refs: List = []
+        parts = []   # per server: (scores, ids) tensors or the reply blob
+        for s in range(table.spec.n if nq else 0):
+            dst = zoo.server_ranks[s]
+            if dst == zoo.rank:
+                parts.append(table._server_nearest(q, k, metric))
+                continue
+            if q_cpu is None:
+                q_cpu = q.cpu().contiguous()
+            hdr = [OP_NEAREST, table.table_id, nq, k, 0, cosine]
+            w, r = self._send_request(dst, hdr, [q_cpu])
+            works += w
+            refs += r
+            blob = torch.empty(nq * k * 12, dtype=torch.uint8)
+            works.append(dist.irecv(blob, dst, group=self.rep))
+            parts.append(blob)
+        for w in works:
+            w.wait()
+        scores, ids = [], []
+        for p in parts:
+            if isinstance(p, tuple):
+                scores.append(p[0])
+                ids.append(p[1])
+            else:
+                ids.append(p[:nq * k * 8].view(torch.int64).view(nq, k)
+                           .to(table.device))
+                scores.append(p[nq * k * 8:].view(torch.float32).view(nq, k)
+                              .to(table.device))
+        if not scores:   # Q == 0: nothing was asked of anyone
+            return (torch.empty(0, 0, dtype=torch.float32,
+                                device=table.device),
+                    torch.empty(0, 0, dtype=torch.int64, device=table.device))
+        return torch.cat(scores, 1), torch.cat(ids, 1)
+
     def kv_add(self, table, keys: torch.Tensor, vals: torch.Tensor):
         """KVTable add: key % num_servers sharding (kv_table.h:49)."""
         zoo = self.zoo
@@ -476,6 +525,21 @@ class AsyncEngine:
     def _serve_one(self, src: int, op: int, tid: int, n_keys: int,
                    n_vals: int, want_ack: bool, has_opt: bool) -> None:
         table = self._table(tid)
+        if op == OP_NEAREST:
+            # n_keys = Q (> 0: an empty search sends nothing), n_vals = k,
+            # has_opt = cosine; the blob is the Q fp32 queries
+            blob = torch.empty(n_keys * table.num_col * 4, dtype=torch.uint8)
+            dist.recv(blob, src, group=self.req)
+            q = blob.view(torch.float32).view(n_keys, table.num_col)
+            with monitor("server.process_get"):
+                scores, ids = table._server_nearest(
+                    q.to(table.device), n_vals,
+                    "cosine" if has_opt else "dot")
+            dist.send(torch.cat(
+                [ids.cpu().contiguous().view(torch.uint8).view(-1),
+                 scores.cpu().contiguous().view(torch.uint8).view(-1)]),
+                src, group=self.rep)
+            return
         # One blob recv mirrors the worker's one blob send (layout in
         # _send_request: [opt][keys][vals], 8-byte aligned sections)
         vals_dtype = None

@@ -8,6 +8,8 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <cstdint>
+#include <limits>
+#include <tuple>
 
 #include "launchers.h"
 
@@ -671,6 +673,43 @@ void lr_ftrl_scatter(torch::Tensor zn, torch::Tensor keys,
                             (float)l2, B, K, cur_stream());
 }
 
+// (scores [Q,k] fp32, ids [Q,k] int64, global) of the k nearest shard rows
+// per query, or None when the launcher refuses (the caller takes its torch
+// path). Slots past the shard's rows are (-inf, INT64_MAX).
+c10::optional<std::tuple<torch::Tensor, torch::Tensor>> row_topk(
+    torch::Tensor shard, torch::Tensor queries, int64_t k, bool cosine,
+    int64_t row_offset) {
+  check_f32(shard, "shard"); check_f32(queries, "queries");
+  TORCH_CHECK(shard.dim() == 2 && queries.dim() == 2 &&
+              shard.size(1) == queries.size(1),
+              "shard [R,cols] and queries [Q,cols] shape mismatch");
+  TORCH_CHECK(shard.device() == queries.device(),
+              "shard and queries must share a device");
+  TORCH_CHECK(k >= 1 && k <= 64, "k must be in 1..64 (got ", k, ")");
+  int64_t R = shard.size(0), cols = shard.size(1), Q = queries.size(0);
+  int waves = 0;
+  int chunk = Q ? mv_row_topk_plan(R, cols, Q, &waves) : 1;
+  if (!chunk) return c10::nullopt;
+  auto iopt = shard.options().dtype(torch::kInt64);
+  if (!Q || !R)
+    return std::make_tuple(
+        torch::full({Q, k}, -std::numeric_limits<float>::infinity(),
+                    shard.options()),
+        torch::full({Q, k}, std::numeric_limits<int64_t>::max(), iopt));
+  // the merge writes every one of the Q*k slots
+  auto scores = torch::empty({Q, k}, shard.options());
+  auto ids = torch::empty({Q, k}, iopt);
+  auto part_s = torch::empty({(int64_t)chunk * waves * k}, shard.options());
+  auto part_i = torch::empty({(int64_t)chunk * waves * k},
+                             shard.options().dtype(torch::kInt32));
+  int ok = mv_launch_row_topk(f32(shard), f32(queries), f32(part_s),
+                              part_i.data_ptr<int>(), f32(scores),
+                              ids.data_ptr<int64_t>(), R, cols, Q, k,
+                              cosine ? 1 : 0, row_offset, cur_stream());
+  TORCH_CHECK(ok, "row_topk: launcher refused a planned request");
+  return std::make_tuple(scores, ids);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -790,6 +829,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("vals"), py::arg("b1"), py::arg("b2"), py::arg("step"),
         py::arg("rbc2"), py::arg("decay"), py::arg("eps"),
         py::arg("perm") = py::none());
+  m.def("row_topk", &row_topk,
+        "nearest rows: (scores [Q,k], global ids [Q,k]) of the k best shard "
+        "rows per query, dot or cosine; None when one query exceeds the LDS "
+        "budget (caller uses torch ops)",
+        py::arg("shard"), py::arg("queries"), py::arg("k"),
+        py::arg("cosine"), py::arg("row_offset") = 0);
   m.def("w2v_train", &w2v_train,
         "K9-K11: fused word2vec block training (skip-gram/CBOW, NS/HS, "
         "optional adagrad)");

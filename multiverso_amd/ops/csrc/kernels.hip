@@ -1973,3 +1973,241 @@ extern "C" int mv_launch_lr_dense_fwd(const float* X, const float* W,
   });
 }
 
+
+// ---------------------------------------------------------------------------
+// Nearest rows (MatrixTable.nearest_rows): the k best rows of the shard for
+// each of Q queries, in two plain launches with no atomics and no
+// cross-workgroup communication.
+//
+// Ordering rule, used at every level (inside a wave, across waves, across
+// shards in tables/matrix_table.py merge_topk): candidate a comes before b
+// when a.score > b.score, or the scores are equal and a.id < b.id. A NaN
+// score enters selection as -inf. An empty slot is (-inf, TOPK_EMPTY), an
+// id above every real row, so it never comes before a real candidate.
+//
+// k_row_topk<Q, COSINE>: the queries are staged once per workgroup into LDS
+// ([col][Q|1], the odd stride of k_lr_dense_fwd), one 64-lane wave takes one
+// row at a time, lanes e-strided over it with Q fma accumulators each (and
+// rr = sum x*x under cosine), wave_sum leaves all Q scores on every lane.
+// The shard is read exactly once. A row's score depends on the row, the
+// query and num_col only (fixed lane assignment, fixed butterfly), never on
+// the wave that computed it, so the result does not depend on the grid.
+// Each wave keeps Q sorted lists, lane j holding the j-th best (score, local
+// row) so far, and stores them to the partials buffer at the end.
+//
+// k_topk_merge: one workgroup per query streams that query's partials
+// through the same insertion routine and writes the final k pairs with
+// global ids. The partials are laid out [Q][waves][k], not [waves][Q][k]:
+// a query's candidates are then one contiguous run that the merge reads 64
+// at a time, fully coalesced, whatever k is.
+// ---------------------------------------------------------------------------
+
+#define TOPK_EMPTY 0x7fffffff
+// partials stay small: 1024 blocks of 4 waves hold 16 waves on each of the
+// 256 CUs, and 4096 lists of 64 pairs for 16 queries are 32 MiB
+#define ROW_TOPK_GRID 1024
+// the default dynamic LDS allowance of a launch; two such workgroups still
+// fit a CU's 160 KiB
+#define ROW_TOPK_LDS (64 * 1024)
+#define MERGE_WAVES (COPY_BLOCK / WAVE)
+// 64-column chunks of its next row that a scanning wave loads ahead
+#define TOPK_PF 4
+
+static __device__ __forceinline__ bool topk_before(float sa, int ia, float sb,
+                                                   int ib) {
+  return sa > sb || (sa == sb && ia < ib);
+}
+
+// value of lane `src` (wave-uniform) on every lane
+static __device__ __forceinline__ float lane_bcast(float v, int src) {
+  return __builtin_bit_cast(
+      float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
+}
+static __device__ __forceinline__ int lane_bcast(int v, int src) {
+  return __builtin_amdgcn_readlane(v, src);
+}
+
+// Offers (s, id), the same on all 64 lanes, to the sorted list whose j-th
+// entry lane j holds in (ls, li); the list keeps its first k entries in
+// order. All 64 lanes come in and stay together: the one branch is taken by
+// the whole wave or by none of it, so the ballot and the shuffles inside
+// see every lane. Lanes from k up only ever hold entries that fell off the
+// end; nobody reads them.
+static __device__ __forceinline__ void topk_insert(float& ls, int& li, float s,
+                                                   int id, int k, int lane) {
+  s = (s != s) ? -INFINITY : s;
+  if (!topk_before(s, id, lane_bcast(ls, k - 1), lane_bcast(li, k - 1)))
+    return;
+  int pos = __popcll(__ballot(topk_before(ls, li, s, id)));
+  float us = __shfl_up(ls, 1, 64);
+  int ui = __shfl_up(li, 1, 64);
+  if (lane > pos) { ls = us; li = ui; }
+  if (lane == pos) { ls = s; li = id; }
+}
+
+// Offers 64 candidates, lane j holding the j-th, to the list: one ballot
+// finds those that come before the list's last entry, and only they go
+// through topk_insert, which tests each against the list as it then stands.
+static __device__ __forceinline__ void topk_insert_lanes(float& ls, int& li,
+                                                         float cs, int ci,
+                                                         int k, int lane) {
+  unsigned long long m = __ballot(
+      topk_before(cs, ci, lane_bcast(ls, k - 1), lane_bcast(li, k - 1)));
+  while (m) {
+    int j = __ffsll(m) - 1;
+    m &= m - 1;
+    topk_insert(ls, li, lane_bcast(cs, j), lane_bcast(ci, j), k, lane);
+  }
+}
+
+template <int Q, bool COSINE>
+__global__ __launch_bounds__(BLOCK) void k_row_topk(
+    const float* __restrict__ shard, const float* __restrict__ queries,
+    float* __restrict__ part_s, int* __restrict__ part_i, int R, int cols,
+    int k) {
+  extern __shared__ float qlds[];  // [cols][Q|1]
+  constexpr int S = Q | 1;  // odd stride: (S*lane) % 64 banks all distinct
+  for (int t = threadIdx.x; t < cols * Q; t += BLOCK)
+    qlds[(t % cols) * S + t / cols] = queries[t];
+  __syncthreads();
+  const Wave wv = this_wave(BLOCK);
+  float ls[Q];
+  int li[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) { ls[q] = -INFINITY; li[q] = TOPK_EMPTY; }
+  // A wave's NEXT row is already on its way while the current one is
+  // reduced and offered to the lists: the first TOPK_PF chunks of 64 columns
+  // (the whole row up to 256 columns) are loaded one row ahead. Without it
+  // a wave has one row's loads in flight, waits out their latency, then
+  // runs the butterfly and the insertions with nothing outstanding
+  // (profiles/nearest_rows.md). Each lane still adds its columns in
+  // ascending order, so the scores are the same bits.
+  float xn[TOPK_PF];
+  auto fetch = [&](int r) {
+    const float* __restrict__ row = shard + (int64_t)r * cols;
+#pragma unroll
+    for (int j = 0; j < TOPK_PF; ++j) {
+      int e = wv.lane + WAVE * j;
+      xn[j] = e < cols ? row[e] : 0.f;
+    }
+  };
+  if (wv.id < R) fetch(wv.id);
+  for (int r = wv.id; r < R; r += wv.n) {
+    const float* __restrict__ row = shard + (int64_t)r * cols;
+    float x[TOPK_PF];
+#pragma unroll
+    for (int j = 0; j < TOPK_PF; ++j) x[j] = xn[j];
+    if ((int64_t)r + wv.n < R) fetch(r + wv.n);
+    float acc[Q] = {};
+    float rr = 0.f;
+    auto term = [](const float* qr, int q) { return qr[q]; };
+#pragma unroll
+    for (int j = 0; j < TOPK_PF; ++j) {
+      int e = wv.lane + WAVE * j;
+      if (e < cols) {
+        add_feature(acc, x[j], qlds + e * S, Q, term);
+        if (COSINE) rr += x[j] * x[j];
+      }
+    }
+    for (int e = wv.lane + WAVE * TOPK_PF; e < cols; e += WAVE) {
+      float xe = row[e];
+      add_feature(acc, xe, qlds + e * S, Q, term);
+      if (COSINE) rr += xe * xe;
+    }
+    wave_sum(acc);
+    float rinv = 1.f;
+    if (COSINE) {
+      rr = wave_sum(rr);
+      rinv = 1.f / sqrtf(rr);
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      // a zero-norm row scores exactly 0; a NaN norm stays NaN (-> -inf)
+      float s = COSINE ? (rr == 0.f ? 0.f : acc[q] * rinv) : acc[q];
+      topk_insert(ls[q], li[q], s, r, k, wv.lane);
+    }
+  }
+  if (wv.lane < k) {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      int64_t at = ((int64_t)q * wv.n + wv.id) * k + wv.lane;
+      part_s[at] = ls[q];
+      part_i[at] = li[q];
+    }
+  }
+}
+
+__global__ __launch_bounds__(COPY_BLOCK) void k_topk_merge(
+    const float* __restrict__ part_s, const int* __restrict__ part_i,
+    float* __restrict__ out_s, int64_t* __restrict__ out_i, int n, int k,
+    int64_t row_offset) {
+  __shared__ float ms[COPY_BLOCK];
+  __shared__ int mi[COPY_BLOCK];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const float* __restrict__ ps = part_s + (int64_t)blockIdx.x * n;
+  const int* __restrict__ pi = part_i + (int64_t)blockIdx.x * n;
+  float ls = -INFINITY;
+  int li = TOPK_EMPTY;
+  for (int base = w * WAVE; base < n; base += COPY_BLOCK) {
+    int j = base + lane;
+    float cs = j < n ? ps[j] : -INFINITY;
+    int ci = j < n ? pi[j] : TOPK_EMPTY;
+    topk_insert_lanes(ls, li, cs, ci, k, lane);
+  }
+  ms[threadIdx.x] = ls;
+  mi[threadIdx.x] = li;
+  __syncthreads();
+  if (w) return;
+  for (int o = 1; o < MERGE_WAVES; ++o)
+    topk_insert_lanes(ls, li, ms[o * WAVE + lane], mi[o * WAVE + lane], k,
+                      lane);
+  if (lane < k) {
+    int64_t at = (int64_t)blockIdx.x * k + lane;
+    out_s[at] = ls;
+    out_i[at] = li == TOPK_EMPTY ? INT64_MAX : li + row_offset;
+  }
+}
+
+// queries one pass can take: the most, up to 16 and Q, whose [cols][q|1]
+// image fits the LDS budget; 0 when a single query does not
+static int row_topk_chunk(int64_t cols, int64_t Q) {
+  int64_t c = Q < 16 ? Q : 16;
+  while (c > 0 && (size_t)cols * (c | 1) * sizeof(float) > ROW_TOPK_LDS) --c;
+  return (int)c;
+}
+
+extern "C" int mv_row_topk_plan(int64_t R, int64_t cols, int64_t Q,
+                                int* waves) {
+  *waves = grid_for_cap((R + 3) / 4 * BLOCK, ROW_TOPK_GRID) * (BLOCK / WAVE);
+  // row indices are ints, and the row loop steps one past R by `waves`
+  if (R > INT32_MAX - ROW_TOPK_GRID * (BLOCK / WAVE) || cols < 1) return 0;
+  return row_topk_chunk(cols, Q);
+}
+
+extern "C" int mv_launch_row_topk(const float* shard, const float* queries,
+                                  float* part_s, int* part_i, float* out_s,
+                                  int64_t* out_i, int64_t R, int64_t cols,
+                                  int64_t Q, int64_t k, int cosine,
+                                  int64_t row_offset, hipStream_t s) {
+  int waves;
+  int chunk = mv_row_topk_plan(R, cols, Q, &waves);
+  if (!chunk || k < 1 || k > WAVE) return 0;
+  if (!R) return 1;
+  // every pass reuses the one partials buffer: the stream orders the merge
+  // of a pass before the scan of the next
+  for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
+    int64_t qc = Q - q0 < chunk ? Q - q0 : chunk;
+    size_t lds = (size_t)cols * (qc | 1) * sizeof(float);
+    with_exact_k<1, 16>(qc, [&](auto qt) {
+      constexpr int QT = decltype(qt)::value;
+      auto* kernel = cosine ? k_row_topk<QT, true> : k_row_topk<QT, false>;
+      kernel<<<waves / (BLOCK / WAVE), BLOCK, lds, s>>>(
+          shard, queries + q0 * cols, part_s, part_i, (int)R, (int)cols,
+          (int)k);
+    });
+    k_topk_merge<<<(int)qc, COPY_BLOCK, 0, s>>>(
+        part_s, part_i, out_s + q0 * k, out_i + q0 * k, (int)(waves * k),
+        (int)k, row_offset);
+  }
+  return 1;
+}

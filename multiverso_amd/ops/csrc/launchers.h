@@ -110,4 +110,15 @@ void mv_launch_lr_dense_post(float*, const float*, const float*, float*,
 int mv_launch_lr_dense_fwd(const float*, const float*, const float*,
                            const float*, float*, float*, float, int64_t,
                            int64_t, int64_t, int, hipStream_t);
+// nearest rows: plan (R, cols, Q, &waves) returns the queries one pass takes,
+// 0 when the launcher cannot run the request (one query's cols*4 bytes exceed
+// the LDS budget), and in `waves` the lists per query the partials must hold.
+// launch (shard, queries, part_scores [min(Q,16)*waves*k], part_rows (same),
+// out_scores [Q,k], out_ids [Q,k], R, cols, Q, k, cosine, row_offset) returns
+// 0 on the same refusal, having launched nothing. R == 0 launches nothing
+// and leaves the outputs as they are.
+int mv_row_topk_plan(int64_t, int64_t, int64_t, int*);
+int mv_launch_row_topk(const float*, const float*, float*, int*, float*,
+                       int64_t*, int64_t, int64_t, int64_t, int64_t, int,
+                       int64_t, hipStream_t);
 }

@@ -36,6 +36,11 @@ MI355X mapping:
   per worker) and added to the next delta. Row-keyed ops, Get, Store and
   Load are unfiltered and leave the residual alone.
 
+- ``nearest_rows`` = top-k row search where the shard lives: each owner scans
+  its rows once (k_row_topk + k_topk_merge) and only ``k`` (score, id) pairs
+  per query per shard cross the wire; ``merge_topk`` holds the one ordering
+  rule. float32 tables, ``k <= 64``, dot or cosine.
+
 Sparse/stale-aware Get (SparseMatrixTable's per-(worker,row) freshness
 bitmap) is implemented in sparse_matrix.py on top of this class; it takes no
 ``wire_dtype``.
@@ -47,11 +52,39 @@ from typing import Optional, Tuple
 
 import torch
 
-from ..comm import Handle, ShardSpec, all_to_all_rows, all_to_all_values
+from ..comm import (Handle, ShardSpec, all_to_all_rows, all_to_all_values,
+                    exchange_sizes)
 from ..dashboard import monitor
 from ..log import CHECK
 from ..updaters import AddOption
 from .dense import DenseTable
+
+# nearest_rows: the largest k (one list slot per lane of a 64-lane wave) and
+# the id of an empty slot, above every real row
+MAX_NEAREST = 64
+EMPTY_ID = torch.iinfo(torch.int64).max
+
+
+def merge_topk(scores: torch.Tensor, ids: torch.Tensor, k: int
+               ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The first ``k`` of ``[Q, m]`` candidates per query under the ordering
+    rule of nearest_rows, defined here and in kernels.hip (topk_before) and
+    nowhere else: a comes before b when ``a.score > b.score``, or the scores
+    are equal and ``a.id < b.id``. A NaN score counts as ``-inf``. An empty
+    slot is ``(-inf, EMPTY_ID)``; it sorts behind every real candidate, so it
+    is dropped whenever ``k`` real ones exist, and fills the tail (``m < k``
+    included) when they do not."""
+    scores = torch.where(scores.isnan(),
+                         torch.full_like(scores, float("-inf")), scores)
+    if scores.shape[1] < k:
+        pad = (scores.shape[0], k - scores.shape[1])
+        scores = torch.cat([scores, scores.new_full(pad, float("-inf"))], 1)
+        ids = torch.cat([ids, ids.new_full(pad, EMPTY_ID)], 1)
+    ids, by_id = torch.sort(ids, dim=1, stable=True)
+    scores = scores.gather(1, by_id)
+    scores, by_score = torch.sort(scores, dim=1, descending=True, stable=True)
+    return (scores[:, :k].contiguous(),
+            ids.gather(1, by_score)[:, :k].contiguous())
 
 
 class MatrixTable(DenseTable):
@@ -187,6 +220,106 @@ class MatrixTable(DenseTable):
     def _server_get_rows(self, local_ids: torch.Tensor) -> torch.Tensor:
         with self._shard_lock:
             return self._gather_local(local_ids)
+
+    # ---- nearest rows: top-k row search where the shard lives ----
+    def nearest_rows(self, queries, k: int, metric: str = "cosine"
+                     ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The ``k`` rows of the table closest to each query: returns
+        ``(scores, ids)``, float32 ``[Q, k]`` and int64 ``[Q, k]`` (global row
+        ids), on the table's device, best first in merge_topk's order.
+
+        ``queries`` is ``[Q, num_col]`` or ``[num_col]`` (one query, the
+        result is ``[1, k]``), any device and float dtype; ``Q == 0`` returns
+        two ``[0, k]`` tensors. ``1 <= k <= min(64, num_row)``: 64 is one
+        list slot per lane of a wave, the same limit on CPU and GPU.
+        ``metric="dot"`` scores row r as ``sum_e r[e]*q[e]``; ``"cosine"``
+        normalises the queries here (``q / ||q||``, a zero query stays zero)
+        and scores ``dot(r, q_hat) / ||r||``, a zero-norm row exactly 0.0.
+        What the owner computes is what comes back; nothing is rescaled
+        after selection. Float32 tables only. Queries and results travel as
+        fp32 and int64 whatever the table's wire format.
+
+        Every owner scans its own rows once and keeps its k best per query;
+        only ``k`` pairs per query per shard cross the wire. On the sync
+        plane this is a collective like ``get_rows``: every rank calls it,
+        with its own queries and its own ``Q`` (0 included), and the same
+        ``k`` and ``metric`` (not checked). Updater state and the sparse
+        table's freshness bitmap are not touched."""
+        self.flush()   # a deferred whole-table Add must land first
+        CHECK(self.dtype == torch.float32,
+              f"nearest_rows needs a float32 table, not {self.dtype}")
+        CHECK(metric in ("dot", "cosine"),
+              f"nearest_rows metric {metric!r} is not known "
+              f"('dot' or 'cosine')")
+        CHECK(isinstance(k, int) and 1 <= k <= min(MAX_NEAREST, self.num_row),
+              f"nearest_rows k={k} must be in 1..min({MAX_NEAREST}, num_row="
+              f"{self.num_row})")
+        q = torch.as_tensor(queries)
+        CHECK(q.is_floating_point(), "nearest_rows queries must be float")
+        q = q.to(self.device, torch.float32)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        CHECK(q.dim() == 2 and q.shape[1] == self.num_col,
+              f"nearest_rows queries must be [Q, {self.num_col}], got "
+              f"{tuple(q.shape)}")
+        # contiguous first: the norm of a strided view may round differently
+        q = q.contiguous()
+        if metric == "cosine":
+            n = torch.linalg.vector_norm(q, dim=1, keepdim=True)
+            q = torch.where(n > 0, q / n, q)
+        eng = self.engine
+        with monitor("worker.nearest_rows"):
+            if eng is not None:
+                CHECK(self.zoo.is_worker,
+                      "ps_role=server ranks issue no searches")
+                s, i = eng.nearest(self, q, k, metric)
+            elif self.zoo.size > 1:
+                s, i = self._nearest_exchange(q, k, metric)
+            else:
+                # one owner holds every row (k <= num_row: no empty slot)
+                # and its selection already is the ordering rule's
+                return self._server_nearest(q, k, metric)
+            return merge_topk(s, i, k)
+
+    def _nearest_exchange(self, q: torch.Tensor, k: int, metric: str):
+        """Sync plane: my queries to every server, ``k`` candidates per query
+        back from each; returns them as ``[Q, n*k]``. The counts ride the
+        control lane."""
+        n, nq = self.zoo.size, q.shape[0]
+        theirs = exchange_sizes([nq] * n)
+        mine = [nq] * n
+        in_q = all_to_all_values(q.reshape(-1).repeat(n), mine, theirs,
+                                 self.num_col)
+        s, i = self._server_nearest(in_q.view(-1, self.num_col), k, metric)
+        s = all_to_all_values(s.reshape(-1), theirs, mine, k)
+        i = all_to_all_values(i.reshape(-1), theirs, mine, k)
+        return (s.view(n, nq, k).transpose(0, 1).reshape(nq, n * k),
+                i.view(n, nq, k).transpose(0, 1).reshape(nq, n * k))
+
+    def _server_nearest(self, queries: torch.Tensor, k: int, metric: str
+                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The owned shard's ``k`` best rows for each query (fp32 ``[Q,
+        num_col]`` on the table's device, already normalised under cosine):
+        ``(scores [Q,k], global ids [Q,k])``, padded with empty slots where
+        the shard has fewer than ``k`` rows. k_row_topk + k_topk_merge on GPU;
+        torch ops on CPU and where the launcher refuses (one query larger
+        than its LDS budget)."""
+        with self._shard_lock, monitor("server.nearest_rows"):
+            if self.shard.is_cuda:
+                from .. import ops
+                got = ops.module(required=True).row_topk(
+                    self.shard, queries, k, metric == "cosine",
+                    self.row_offset)
+                if got is not None:
+                    return got
+            s = queries @ self.shard.t()
+            if metric == "cosine":
+                norm = torch.linalg.vector_norm(self.shard, dim=1)
+                s = torch.where(norm == 0, torch.zeros_like(s), s / norm)
+            ids = torch.arange(self.row_offset,
+                               self.row_offset + self.local_rows,
+                               device=s.device).expand(s.shape[0], -1)
+            return merge_topk(s, ids, k)
 
     # ---- checkpoint (matrix_table.cpp:457-464) ----
     def store(self, path: str) -> None:
