@@ -674,11 +674,14 @@ void lr_ftrl_scatter(torch::Tensor zn, torch::Tensor keys,
 }
 
 // (scores [Q,k] fp32, ids [Q,k] int64, global) of the k nearest shard rows
-// per query, or None when the launcher refuses (the caller takes its torch
-// path). Slots past the shard's rows are (-inf, INT64_MAX).
-c10::optional<std::tuple<torch::Tensor, torch::Tensor>> row_topk(
-    torch::Tensor shard, torch::Tensor queries, int64_t k, bool cosine,
-    int64_t row_offset) {
+// per query, or None when the launcher refuses (the caller takes its next
+// path). Slots past the shard's rows are (-inf, INT64_MAX). The two scans
+// (k_row_topk, k_row_topk_mm) share the plan and launch signatures, and this.
+using TopkResult = c10::optional<std::tuple<torch::Tensor, torch::Tensor>>;
+template <class Plan, class Launch>
+TopkResult topk_with(Plan plan, Launch launch, torch::Tensor shard,
+                     torch::Tensor queries, int64_t k, bool cosine,
+                     int64_t row_offset) {
   check_f32(shard, "shard"); check_f32(queries, "queries");
   TORCH_CHECK(shard.dim() == 2 && queries.dim() == 2 &&
               shard.size(1) == queries.size(1),
@@ -688,7 +691,7 @@ c10::optional<std::tuple<torch::Tensor, torch::Tensor>> row_topk(
   TORCH_CHECK(k >= 1 && k <= 64, "k must be in 1..64 (got ", k, ")");
   int64_t R = shard.size(0), cols = shard.size(1), Q = queries.size(0);
   int waves = 0;
-  int chunk = Q ? mv_row_topk_plan(R, cols, Q, &waves) : 1;
+  int chunk = Q ? plan(R, cols, Q, &waves) : 1;
   if (!chunk) return c10::nullopt;
   auto iopt = shard.options().dtype(torch::kInt64);
   if (!Q || !R)
@@ -702,12 +705,25 @@ c10::optional<std::tuple<torch::Tensor, torch::Tensor>> row_topk(
   auto part_s = torch::empty({(int64_t)chunk * waves * k}, shard.options());
   auto part_i = torch::empty({(int64_t)chunk * waves * k},
                              shard.options().dtype(torch::kInt32));
-  int ok = mv_launch_row_topk(f32(shard), f32(queries), f32(part_s),
-                              part_i.data_ptr<int>(), f32(scores),
-                              ids.data_ptr<int64_t>(), R, cols, Q, k,
-                              cosine ? 1 : 0, row_offset, cur_stream());
+  int ok = launch(f32(shard), f32(queries), f32(part_s),
+                  part_i.data_ptr<int>(), f32(scores),
+                  ids.data_ptr<int64_t>(), R, cols, Q, k, cosine ? 1 : 0,
+                  row_offset, cur_stream());
   TORCH_CHECK(ok, "row_topk: launcher refused a planned request");
   return std::make_tuple(scores, ids);
+}
+
+TopkResult row_topk(torch::Tensor shard, torch::Tensor queries, int64_t k,
+                    bool cosine, int64_t row_offset) {
+  return topk_with(mv_row_topk_plan, mv_launch_row_topk, shard, queries, k,
+                   cosine, row_offset);
+}
+
+// the MFMA scan for query batches, whatever Q is
+TopkResult row_topk_mm(torch::Tensor shard, torch::Tensor queries, int64_t k,
+                       bool cosine, int64_t row_offset) {
+  return topk_with(mv_row_topk_mm_plan, mv_launch_row_topk_mm, shard, queries,
+                   k, cosine, row_offset);
 }
 
 }  // namespace
@@ -833,6 +849,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "nearest rows: (scores [Q,k], global ids [Q,k]) of the k best shard "
         "rows per query, dot or cosine; None when one query exceeds the LDS "
         "budget (caller uses torch ops)",
+        py::arg("shard"), py::arg("queries"), py::arg("k"),
+        py::arg("cosine"), py::arg("row_offset") = 0);
+  m.def("row_topk_mm", &row_topk_mm,
+        "nearest rows for query batches (MFMA scan, 64 queries per pass): "
+        "the contract of row_topk; None past 2048 columns",
         py::arg("shard"), py::arg("queries"), py::arg("k"),
         py::arg("cosine"), py::arg("row_offset") = 0);
   m.def("w2v_train", &w2v_train,

@@ -2211,3 +2211,231 @@ extern "C" int mv_launch_row_topk(const float* shard, const float* queries,
   }
   return 1;
 }
+
+// ---------------------------------------------------------------------------
+// Nearest rows for query batches: k_row_topk_mm<NB, COSINE>, the first kernel
+// here past the matrix cores' ridge (Q/2 FLOP per shard byte). The scores of
+// a pass are a GEMM, S = shard . Qt, on v_mfma_f32_32x32x2_f32: fp32 in, fp32
+// accumulate, so integer-valued data stays exact and the oracle's fp32
+// tolerance holds as it is.
+//
+// A workgroup of 4 waves takes 128 consecutive rows at a time, wave w rows
+// 32w..32w+31, against QT = 32*NB queries (NB accumulator blocks of 16 VGPRs
+// sharing every A fragment), in panels of 64 columns through LDS:
+//   A [128][68]   the rows' panel, loaded from global as 256-byte row
+//                 segments (float4 per thread where cols % 4 == 0, one float
+//                 otherwise) and read back as one ds_read_b128 per lane and 4
+//                 MFMAs: lane (row, half) holds columns 8s+4*half .. +3 of
+//                 step s, so MFMA t of the step multiplies column 8s+t
+//                 (lanes 0-31) and 8s+4+t (lanes 32-63). Stride 68 keeps the
+//                 16-byte alignment and turns 16 rows into 64 distinct banks.
+//   B [64][QT+1]  the queries' panel, [col][query]: a B fragment is 32
+//                 consecutive floats, and the odd stride spreads the
+//                 transposing stores over the banks.
+// Rows past R, queries past the batch and columns past cols are zeros in
+// both images; the MFMA loop has no guard, only a step count that stops at
+// the last panel's last 8 columns. rr = sum x*x accumulates on the lane that
+// feeds the value to the A fragment, the two half-wave parts meet once.
+//
+// After the panels the 128 x QT scores go to LDS over the panel images,
+// [query][132], as float4s (an accumulator block holds 4 consecutive rows
+// per lane). Wave w then owns queries w*QT/4 .. and offers each its 128
+// scores 64 at a time through topk_insert_lanes; one list per (workgroup,
+// query) lives across the grid-stride loop over row tiles, in registers,
+// statically indexed. Partials are [query][workgroup][k] for k_topk_merge.
+// A score depends on the row, the query, cols and the constants here, never
+// on the grid or on the row's place in a tile.
+// ---------------------------------------------------------------------------
+
+#define MM_ROWS 128   // rows per workgroup tile, 32 per wave
+#define MM_PANEL 64   // columns per LDS panel
+#define MM_AS 68      // A row stride
+#define MM_SS 132     // score row stride: 16-byte aligned, 4 banks per query
+// two workgroups are resident on each of the 256 CUs (about 200 registers
+// a lane; their 51 KiB of LDS would allow three), so 512 keeps every
+// workgroup persistent and bounds the partials at 512 lists per query
+// (16 MiB of pairs for 64 queries at k = 64)
+#define MM_GRID 512
+// the word2vec kernels' own limit; wider rows take k_row_topk
+#define MM_MAX_COLS 2048
+
+typedef float v16f __attribute__((ext_vector_type(16)));
+
+// no packed fp32 arithmetic in this kernel, the scalar forms only (a device
+// target feature; the host pass does not know it)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MM_SCALAR_FP32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define MM_SCALAR_FP32
+#endif
+
+template <int NB, bool COSINE>
+__global__ __launch_bounds__(BLOCK) MM_SCALAR_FP32 void k_row_topk_mm(
+    const float* __restrict__ shard, const float* __restrict__ queries,
+    float* __restrict__ part_s, int* __restrict__ part_i, int R, int cols,
+    int Q, int k) {
+  constexpr int QT = 32 * NB, QS = QT + 1, QW = QT / 4;
+  constexpr int A_SZ = MM_ROWS * MM_AS, B_SZ = MM_PANEL * QS;
+  constexpr int S_SZ = QT * MM_SS;
+  __shared__ __attribute__((aligned(16)))
+      float lds[A_SZ + B_SZ > S_SZ ? A_SZ + B_SZ : S_SZ];
+  __shared__ float rrs[MM_ROWS];
+  float* const A = lds;
+  float* const B = lds + A_SZ;
+  float* const sc = lds;  // over A and B once the panels are consumed
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int j = lane & 31, half = lane >> 5;
+  const bool wide = (cols & 3) == 0;
+  float ls[QW];
+  int li[QW];
+#pragma unroll
+  for (int t = 0; t < QW; ++t) { ls[t] = -INFINITY; li[t] = TOPK_EMPTY; }
+  const int tiles = (R + MM_ROWS - 1) / MM_ROWS;
+  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int row0 = tile * MM_ROWS;
+    // the tile is one contiguous run of the shard; row0 is a multiple of
+    // 128, so with cols % 4 == 0 every float4 below is 16-byte aligned
+    const float* __restrict__ src = shard + (int64_t)row0 * cols;
+    const int nrows = R - row0 < MM_ROWS ? R - row0 : MM_ROWS;
+    v16f acc[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) acc[b][v] = 0.f;
+    float rr = 0.f;
+    for (int c0 = 0; c0 < cols; c0 += MM_PANEL) {
+      __syncthreads();  // the last readers of A, B (or sc) are through
+      if (wide) {
+        const int c = 4 * (tid & 15);
+#pragma unroll
+        for (int i = 0; i < MM_ROWS / 16; ++i) {
+          const int r = i * 16 + (tid >> 4);
+          float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (r < nrows && c0 + c < cols)
+            x = *reinterpret_cast<const float4*>(src + (int64_t)r * cols +
+                                                 c0 + c);
+          *reinterpret_cast<float4*>(A + r * MM_AS + c) = x;
+        }
+      } else {
+#pragma unroll 8
+        for (int i = 0; i < MM_ROWS / 4; ++i) {
+          const int r = i * 4 + w;
+          A[r * MM_AS + lane] = (r < nrows && c0 + lane < cols)
+                                    ? src[(int64_t)r * cols + c0 + lane]
+                                    : 0.f;
+        }
+      }
+#pragma unroll 4
+      for (int i = 0; i < QT / 4; ++i) {
+        const int q = i * 4 + w;
+        B[lane * QS + q] = (q < Q && c0 + lane < cols)
+                               ? queries[(int64_t)q * cols + c0 + lane]
+                               : 0.f;
+      }
+      __syncthreads();
+      const int left = cols - c0;
+      const int steps = left < MM_PANEL ? (left + 7) / 8 : MM_PANEL / 8;
+      const float* __restrict__ ar = A + (w * 32 + j) * MM_AS + 4 * half;
+      const float* __restrict__ br = B + 4 * half * QS + j;
+      for (int s = 0; s < steps; ++s) {
+        const float4 a4 = *reinterpret_cast<const float4*>(ar + 8 * s);
+        const float a[4] = {a4.x, a4.y, a4.z, a4.w};
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+#pragma unroll
+          for (int b = 0; b < NB; ++b)
+            acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(
+                a[t], br[(8 * s + t) * QS + 32 * b], acc[b], 0, 0, 0);
+          if (COSINE) rr += a[t] * a[t];
+        }
+      }
+    }
+    __syncthreads();  // every wave is done with the panels: sc takes over
+    // accumulator v of lane (j, half) is row 8*(v/4) + 4*half + v%4 of the
+    // wave's 32, query j of its block
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        *reinterpret_cast<float4*>(sc + (32 * b + j) * MM_SS + w * 32 +
+                                   8 * g + 4 * half) =
+            make_float4(acc[b][4 * g], acc[b][4 * g + 1], acc[b][4 * g + 2],
+                        acc[b][4 * g + 3]);
+    if (COSINE) {
+      rr += __shfl_xor(rr, 32, 64);
+      if (!half) rrs[w * 32 + j] = rr;
+    }
+    __syncthreads();
+    float rinv[2];
+    bool zero[2];
+    if (COSINE) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const float n = rrs[c * 64 + lane];
+        zero[c] = n == 0.f;
+        rinv[c] = 1.f / sqrtf(n);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < QW; ++t) {
+      const int q = w * QW + t;
+      if (q >= Q) break;  // wave-uniform: queries past the batch have no list
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const int r = c * 64 + lane;
+        float s = sc[q * MM_SS + r];
+        // a zero-norm row scores exactly 0; a NaN norm stays NaN (-> -inf)
+        if (COSINE) s = zero[c] ? 0.f : s * rinv[c];
+        s = (s != s) ? -INFINITY : s;
+        // a row past R is an empty slot: it comes before nothing
+        topk_insert_lanes(ls[t], li[t], r < nrows ? s : -INFINITY,
+                          r < nrows ? row0 + r : TOPK_EMPTY, k, lane);
+      }
+    }
+  }
+  if (lane < k) {
+#pragma unroll
+    for (int t = 0; t < QW; ++t) {
+      const int q = w * QW + t;
+      if (q >= Q) break;
+      int64_t at = ((int64_t)q * gridDim.x + blockIdx.x) * k + lane;
+      part_s[at] = ls[t];
+      part_i[at] = li[t];
+    }
+  }
+}
+
+extern "C" int mv_row_topk_mm_plan(int64_t R, int64_t cols, int64_t Q,
+                                   int* lists) {
+  *lists = grid_for_cap(R, MM_GRID, MM_ROWS);
+  // row indices are ints, and the tile loop steps one past R by the grid
+  if (R > INT32_MAX - (int64_t)MM_GRID * MM_ROWS || cols < 1 ||
+      cols > MM_MAX_COLS)
+    return 0;
+  return Q < 1 ? 1 : Q < 64 ? (int)Q : 64;
+}
+
+extern "C" int mv_launch_row_topk_mm(const float* shard, const float* queries,
+                                     float* part_s, int* part_i, float* out_s,
+                                     int64_t* out_i, int64_t R, int64_t cols,
+                                     int64_t Q, int64_t k, int cosine,
+                                     int64_t row_offset, hipStream_t s) {
+  int lists;
+  int chunk = mv_row_topk_mm_plan(R, cols, Q, &lists);
+  if (!chunk || k < 1 || k > WAVE) return 0;
+  if (!R) return 1;
+  // every pass reuses the one partials buffer: the stream orders the merge
+  // of a pass before the scan of the next
+  for (int64_t q0 = 0; q0 < Q; q0 += chunk) {
+    int64_t qc = Q - q0 < chunk ? Q - q0 : chunk;
+    auto* kernel = qc > 32
+        ? (cosine ? k_row_topk_mm<2, true> : k_row_topk_mm<2, false>)
+        : (cosine ? k_row_topk_mm<1, true> : k_row_topk_mm<1, false>);
+    kernel<<<lists, BLOCK, 0, s>>>(shard, queries + q0 * cols, part_s, part_i,
+                                   (int)R, (int)cols, (int)qc, (int)k);
+    k_topk_merge<<<(int)qc, COPY_BLOCK, 0, s>>>(
+        part_s, part_i, out_s + q0 * k, out_i + q0 * k, (int)(lists * k),
+        (int)k, row_offset);
+  }
+  return 1;
+}

@@ -121,4 +121,13 @@ int mv_row_topk_plan(int64_t, int64_t, int64_t, int*);
 int mv_launch_row_topk(const float*, const float*, float*, int*, float*,
                        int64_t*, int64_t, int64_t, int64_t, int64_t, int,
                        int64_t, hipStream_t);
+// nearest rows for query batches (k_row_topk_mm, the MFMA scan), the same two
+// signatures: plan returns the queries one pass takes (up to 64), 0 when the
+// launcher cannot run the request (R too large for int row indices, or more
+// than 2048 columns), and in `lists` the workgroups, each with one list per
+// query. launch takes partials of min(Q,64)*lists*k pairs.
+int mv_row_topk_mm_plan(int64_t, int64_t, int64_t, int*);
+int mv_launch_row_topk_mm(const float*, const float*, float*, int*, float*,
+                          int64_t*, int64_t, int64_t, int64_t, int64_t, int,
+                          int64_t, hipStream_t);
 }

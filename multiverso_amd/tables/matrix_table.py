@@ -37,8 +37,8 @@ MI355X mapping:
   Load are unfiltered and leave the residual alone.
 
 - ``nearest_rows`` = top-k row search where the shard lives: each owner scans
-  its rows once (k_row_topk + k_topk_merge) and only ``k`` (score, id) pairs
-  per query per shard cross the wire; ``merge_topk`` holds the one ordering
+  its rows once (k_row_topk, from 17 queries k_row_topk_mm, + k_topk_merge)
+  and only ``k`` (score, id) pairs per query per shard cross the wire; ``merge_topk`` holds the one ordering
   rule. float32 tables, ``k <= 64``, dot or cosine.
 
 Sparse/stale-aware Get (SparseMatrixTable's per-(worker,row) freshness
@@ -63,6 +63,9 @@ from .dense import DenseTable
 # the id of an empty slot, above every real row
 MAX_NEAREST = 64
 EMPTY_ID = torch.iinfo(torch.int64).max
+# from this many queries a server scans with k_row_topk_mm (the MFMA scan, 64
+# queries per pass): exactly where k_row_topk would need a second pass
+NEAREST_BATCH = 17
 
 
 def merge_topk(scores: torch.Tensor, ids: torch.Tensor, k: int
@@ -244,7 +247,15 @@ class MatrixTable(DenseTable):
         plane this is a collective like ``get_rows``: every rank calls it,
         with its own queries and its own ``Q`` (0 included), and the same
         ``k`` and ``metric`` (not checked). Updater state and the sparse
-        table's freshness bitmap are not touched."""
+        table's freshness bitmap are not touched.
+
+        A server that receives 17 queries or more scans with the matrix-core
+        kernel (k_row_topk_mm), fewer with k_row_topk. The two sum a dot
+        product in different orders, so a query's scores may differ in the
+        last bits between a call served below that count and one at or above
+        it, both within ``(num_col + 8) * 2^-24 * sum|q_e||r_e|`` of the exact
+        score; on integer-valued data both are exact. On the sync plane the
+        server chooses by the total it received from all ranks."""
         self.flush()   # a deferred whole-table Add must land first
         CHECK(self.dtype == torch.float32,
               f"nearest_rows needs a float32 table, not {self.dtype}")
@@ -301,17 +312,21 @@ class MatrixTable(DenseTable):
         """The owned shard's ``k`` best rows for each query (fp32 ``[Q,
         num_col]`` on the table's device, already normalised under cosine):
         ``(scores [Q,k], global ids [Q,k])``, padded with empty slots where
-        the shard has fewer than ``k`` rows. k_row_topk + k_topk_merge on GPU;
-        torch ops on CPU and where the launcher refuses (one query larger
-        than its LDS budget)."""
+        the shard has fewer than ``k`` rows. On GPU k_row_topk_mm from
+        NEAREST_BATCH queries and k_row_topk below, or where the former
+        refuses (more than 2048 columns), + k_topk_merge; torch ops on CPU and
+        where both launchers refuse (one query larger than the LDS budget)."""
         with self._shard_lock, monitor("server.nearest_rows"):
             if self.shard.is_cuda:
                 from .. import ops
-                got = ops.module(required=True).row_topk(
-                    self.shard, queries, k, metric == "cosine",
-                    self.row_offset)
-                if got is not None:
-                    return got
+                hip = ops.module(required=True)
+                scans = (hip.row_topk_mm, hip.row_topk) \
+                    if queries.shape[0] >= NEAREST_BATCH else (hip.row_topk,)
+                for scan in scans:
+                    got = scan(self.shard, queries, k, metric == "cosine",
+                               self.row_offset)
+                    if got is not None:
+                        return got
             s = queries @ self.shard.t()
             if metric == "cosine":
                 norm = torch.linalg.vector_norm(self.shard, dim=1)

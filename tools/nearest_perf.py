@@ -18,6 +18,16 @@ once, over the time of nearest_rows (both kernels and the two small
 allocations of the binding included); the copy's rate is read + write, 8
 bytes per element. Each line also says whether the two forms agree on the
 ids, compared at the timed size.
+
+  python tools/nearest_perf.py --batch        (profiles/nearest_rows_batch.md)
+
+For Q in {17, 32, 64, 256}, k = 10 and both metrics, on the binding level and
+on normalised queries, in one run, alternating as above:
+
+  row_topk       k_row_topk forced: ceil(Q/16) scans of the shard
+  row_topk_mm    k_row_topk_mm, the MFMA scan: ceil(Q/64) scans
+  K7 copy        as above
+  composition    get + matmul + topk, metric dot only, as a yardstick
 """
 
 import argparse
@@ -51,12 +61,60 @@ def window(call, calls):
     return a.elapsed_time(b) / calls
 
 
+def batch(args, t, hip, dst, g) -> None:
+    shard_bytes = t.shard.numel() * 4
+    for metric in ("cosine", "dot"):
+        for Q in (17, 32, 64, 256):
+            q = torch.randn(Q, args.cols, generator=g, device="cuda")
+            q = q / torch.linalg.vector_norm(q, dim=1, keepdim=True)
+            k, cos = 10, metric == "cosine"
+            forms = {
+                "row_topk": lambda: hip.row_topk(t.shard, q, k, cos, 0),
+                "row_topk_mm": lambda: hip.row_topk_mm(t.shard, q, k, cos, 0),
+                "k7_copy": lambda: hip.nt_copy(dst.view(-1),
+                                               t.shard.view(-1)),
+            }
+            if not cos:
+                forms["composition"] = lambda: composition(t, q, k, metric)
+            for call in forms.values():
+                for _ in range(2):
+                    call()
+            torch.cuda.synchronize()
+            old, new = forms["row_topk"](), forms["row_topk_mm"]()
+            same = bool((old[1].sort(1).values == new[1].sort(1).values).all())
+            times = {name: [] for name in forms}
+            for _ in range(args.windows):
+                for name, call in forms.items():
+                    times[name].append(window(call, args.calls))
+            line = {"rows": args.rows, "cols": args.cols, "metric": metric,
+                    "Q": Q, "k": k}
+            for name, v in times.items():
+                line[name + "_ms"] = round(statistics.median(v), 4)
+                line[name + "_ms_range"] = [round(min(v), 4), round(max(v), 4)]
+            passes = -(-Q // 64)
+            line.update({
+                "speedup_over_row_topk": round(
+                    line["row_topk_ms"] / line["row_topk_mm_ms"], 2),
+                "scan_TB_per_s": round(
+                    passes * shard_bytes / line["row_topk_mm_ms"] / 1e9, 3),
+                "copy_TB_per_s": round(
+                    2 * shard_bytes / line["k7_copy_ms"] / 1e9, 3),
+                "scan_TFLOP_per_s": round(
+                    2.0 * Q * t.shard.numel() / line["row_topk_mm_ms"] / 1e9,
+                    2),
+                "same_id_sets": same,
+                "max_score_diff": float((old[0] - new[0]).abs().max())})
+            print(json.dumps(line), flush=True)
+
+
 def main() -> None:
     p = argparse.ArgumentParser()
     p.add_argument("--rows", type=int, default=1_000_000)
     p.add_argument("--cols", type=int, default=200)
     p.add_argument("--calls", type=int, default=40)
     p.add_argument("--windows", type=int, default=5)
+    p.add_argument("--batch", action="store_true",
+                   help="time the query-batch forms instead")
     args = p.parse_args()
     assert torch.cuda.is_available(), "nearest_perf.py measures on a GPU"
     import multiverso_amd as mv
@@ -69,6 +127,10 @@ def main() -> None:
                               device="cuda"))
     dst = torch.empty_like(t.shard)
     shard_bytes = t.shard.numel() * 4
+    if args.batch:
+        batch(args, t, hip, dst, g)
+        mv.shutdown()
+        return
     for metric in ("cosine", "dot"):
         for Q in (1, 4, 16):
             q = torch.randn(Q, args.cols, generator=g, device="cuda")
