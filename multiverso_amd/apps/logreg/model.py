@@ -28,6 +28,9 @@ from multiverso_amd import ops
 
 from .objective import Batch, DenseBatch, create_objective
 
+# most classes (FTRL outputs, dense columns) the fused kernels serve
+LR_WIDE_MAX = 1024
+
 
 class WorkerSGDSchedule:
     def __init__(self, cfg) -> None:
@@ -220,11 +223,13 @@ class PSModel:
 
     def _dense_fused_ok(self) -> bool:
         """GPU dense minibatch fusion applies to the sigmoid/softmax
-        objectives (K <= 64).  FTRL dense is refused upstream."""
+        objectives (K <= 1024: up to 64 columns through lr_dense_fwd /
+        lr_dense_post, 65..1024 through lr_dense_post_wide).  FTRL dense
+        is refused upstream."""
         from .objective import SigmoidObjective, SoftmaxObjective
-        return (type(self.objective) in (SigmoidObjective,
-                                         SoftmaxObjective)
-                and self.cols <= 64)
+        if type(self.objective) is SoftmaxObjective:
+            return self.cols <= LR_WIDE_MAX   # the wide post is a softmax
+        return type(self.objective) is SigmoidObjective and self.cols <= 64
 
     def _dense_minibatches_fused(self, batches, local) -> float:
         """Dense minibatch loop as 4 GPU ops each (GEMM, fused
@@ -235,7 +240,9 @@ class PSModel:
         then grad = X^T@diff (rocBLAS again) and the SGD/regularizer
         update runs as in-place torch ops.  Numerics match
         objective.gradient + the learning-rate step
-        (tests/test_gpu_kernels.py::test_lr_dense_post_*)."""
+        (tests/test_gpu_kernels.py::test_lr_dense_post_*).  Beyond 64
+        columns the forward is always the GEMM + ``lr_dense_post_wide``
+        (tests/test_gpu_lr_wide.py)."""
         from multiverso_amd import ops as _ops
         from .objective import L1Regular, L2Regular
         hip = _ops.module(required=True)
@@ -252,8 +259,12 @@ class PSModel:
                       else b.labels.float())
             if logits is None or logits.shape[0] != B:
                 logits = torch.empty(B, self.cols, device=self.device)
-            if not hip.lr_dense_fwd(b.x, local, labels, wts,
-                                    logits, loss_acc, 1.0 / B):
+            if self.cols > 64:
+                torch.matmul(b.x, local, out=logits)
+                hip.lr_dense_post_wide(logits, labels, wts, loss_acc,
+                                       1.0 / B)
+            elif not hip.lr_dense_fwd(b.x, local, labels, wts,
+                                      logits, loss_acc, 1.0 / B):
                 # d*K over the LDS budget: rocBLAS GEMM + fused post
                 torch.matmul(b.x, local, out=logits)
                 hip.lr_dense_post(logits, labels, wts, loss_acc,
@@ -272,7 +283,9 @@ class PSModel:
         """Which fused K13/K14 minibatch kernel pair serves this
         objective on GPU ('' = torch path). All three reference
         objectives now have fused forms: sigmoid (1 col), softmax
-        (2..64 classes), ftrl (z|n state, <=32 outputs)."""
+        (2..1024 classes), ftrl (z|n state, <=1024 outputs). Beyond 64
+        classes (32 FTRL outputs) the forward is the class-per-lane
+        kernel; above 1024 the torch path serves."""
         from .objective import (FTRLObjective, SigmoidObjective,
                                 SoftmaxObjective)
         if not local.is_cuda:
@@ -280,10 +293,10 @@ class PSModel:
         if self.cols == 1 and type(self.objective) is SigmoidObjective:
             return "sigmoid"
         if (type(self.objective) is SoftmaxObjective
-                and 2 <= self.cols <= 64):
+                and 2 <= self.cols <= LR_WIDE_MAX):
             return "softmax"
         if (type(self.objective) is FTRLObjective
-                and self.cfg.output_size <= 32):
+                and self.cfg.output_size <= LR_WIDE_MAX):
             return "ftrl"
         return ""
 
@@ -291,7 +304,11 @@ class PSModel:
         """Two HIP kernels per minibatch (fwd + scatter) instead of ~20
         torch ops; numerics match objective.gradient + scatter
         (tests/test_gpu_kernels.py). Returns summed per-batch mean
-        losses (one host sync per chunk instead of per minibatch)."""
+        losses (one host sync per chunk instead of per minibatch).
+        Softmax beyond 64 classes and FTRL beyond 32 outputs run the
+        wide entry points; those refuse labels outside [0, K), which is
+        checked here once per chunk (one more sync per chunk, none per
+        minibatch)."""
         from multiverso_amd import ops as _ops
         hip = _ops.module(required=True)
         from .objective import L1Regular, L2Regular
@@ -304,6 +321,13 @@ class PSModel:
         K = self.cfg.output_size
         wflat = local.view(-1)
         loss_acc = torch.zeros((), device=self.device)
+        wide = K > (32 if kind == "ftrl" else 64)
+        if wide and batches:
+            lo, hi = torch.aminmax(torch.cat([b.labels.float()
+                                              for b in batches]))
+            if not (float(lo) >= 0 and float(hi) < K):
+                raise ValueError(f"labels must lie in [0, {K}) "
+                                 f"(got {float(lo)}..{float(hi)})")
         for b, lidx in zip(batches, lidxs):
             ptr32 = b.ptr.to(torch.int32)
             B = b.size
@@ -317,6 +341,14 @@ class PSModel:
                 lr = self.sched.next_lr()
                 hip.lr_sigmoid_scatter(wflat, lidx, b.vals, ptr32, err, lr,
                                        reg_type, reg_coef)
+            elif kind == "softmax" and wide:
+                err = torch.empty(B * K, device=self.device)
+                hip.lr_softmax_wide_forward(wflat, lidx, b.vals, ptr32,
+                                            labels, wts, err, lossb, K,
+                                            labels_checked=True)
+                lr = self.sched.next_lr()
+                hip.lr_softmax_wide_scatter(wflat, lidx, b.vals, ptr32, err,
+                                            lr, reg_type, reg_coef, K)
             elif kind == "softmax":
                 err = torch.empty(B * K, device=self.device)
                 hip.lr_softmax_forward(wflat, lidx, b.vals, ptr32, labels,
@@ -324,6 +356,16 @@ class PSModel:
                 lr = self.sched.next_lr()
                 hip.lr_softmax_scatter(wflat, lidx, b.vals, ptr32, err, lr,
                                        reg_type, reg_coef, K)
+            elif wide:  # ftrl, 33..1024 outputs
+                o = self.objective
+                err = torch.empty(B * K, device=self.device)
+                hip.lr_ftrl_wide_forward(wflat, lidx, b.vals, ptr32, labels,
+                                         wts, err, lossb, 1.0 / o.alpha_inv,
+                                         o.beta, o.l1, o.l2, K,
+                                         labels_checked=True)
+                hip.lr_ftrl_wide_scatter(wflat, lidx, b.vals, ptr32, err,
+                                         1.0 / o.alpha_inv, o.beta, o.l1,
+                                         o.l2, K)
             else:  # ftrl: state update is lr-free (updater.cpp:79-101)
                 o = self.objective
                 err = torch.empty(B * K, device=self.device)

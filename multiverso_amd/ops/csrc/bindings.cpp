@@ -673,6 +673,119 @@ void lr_ftrl_scatter(torch::Tensor zn, torch::Tensor keys,
                             (float)l2, B, K, cur_stream());
 }
 
+// ---- the class-per-lane ("wide") logreg entry points ------------------------
+// Each takes exactly the class counts its narrow sibling refuses, up to 1024,
+// and makes the same device, contiguity and size checks.
+constexpr int64_t LR_WIDE_MAX = 1024;
+
+void check_softmax_wide_k(const torch::Tensor& w, int64_t K) {
+  TORCH_CHECK(K >= 65 && K <= LR_WIDE_MAX,
+              "wide fused softmax supports 65..1024 classes (got ", K, ")");
+  TORCH_CHECK(w.numel() % K == 0, "w must hold whole rows of K");
+}
+void check_ftrl_wide_k(const torch::Tensor& zn, int64_t K) {
+  TORCH_CHECK(K >= 33 && K <= LR_WIDE_MAX,
+              "wide fused FTRL supports 33..1024 outputs (got ", K, ")");
+  TORCH_CHECK(zn.numel() % (2 * K) == 0,
+              "zn must hold whole rows of 2*K (z | n)");
+}
+
+// Labels outside [0, K) are refused. The check reads device memory (a sync),
+// so a caller that has checked a whole chunk's labels itself passes
+// labels_checked = true (apps/logreg/model.py does, once per chunk).
+void check_labels(const torch::Tensor& labels, int64_t K, bool checked) {
+  if (checked || !labels.numel()) return;
+  float lo = labels.min().item<float>(), hi = labels.max().item<float>();
+  TORCH_CHECK(lo >= 0.f && hi < (float)K, "labels must lie in [0, ", K,
+              ") (got ", lo, "..", hi, ")");
+}
+
+void lr_softmax_wide_forward(torch::Tensor w, torch::Tensor keys,
+                             torch::Tensor vals, torch::Tensor ptr,
+                             torch::Tensor labels,
+                             c10::optional<torch::Tensor> wts,
+                             torch::Tensor err, torch::Tensor loss, int64_t K,
+                             bool labels_checked) {
+  check_f32(w, "w"); check_f32(vals, "vals"); check_f32(labels, "labels");
+  check_f32(err, "err"); check_f32(loss, "loss");
+  check_softmax_wide_k(w, K);
+  int64_t B = check_csr(keys, vals, ptr);
+  TORCH_CHECK(labels.numel() == B && loss.numel() == B, "batch mismatch");
+  TORCH_CHECK(err.numel() == B * K, "err must be [B, K]");
+  const float* wp = opt_weights(wts, B);
+  check_labels(labels, K, labels_checked);
+  mv_launch_lr_softmax_wide_fwd(f32(w), keys.data_ptr<int64_t>(), f32(vals),
+                                ptr.data_ptr<int>(), f32(labels), wp,
+                                f32(err), f32(loss), B, K, cur_stream());
+}
+
+void lr_softmax_wide_scatter(torch::Tensor w, torch::Tensor keys,
+                             torch::Tensor vals, torch::Tensor ptr,
+                             torch::Tensor err, double lr, int64_t reg_type,
+                             double reg_coef, int64_t K) {
+  check_f32(w, "w"); check_f32(vals, "vals"); check_f32(err, "err");
+  check_softmax_wide_k(w, K);
+  int64_t B = check_csr(keys, vals, ptr);
+  TORCH_CHECK(err.numel() == B * K, "err must be [B, K]");
+  mv_launch_lr_softmax_scatter(f32(w), keys.data_ptr<int64_t>(), f32(vals),
+                               ptr.data_ptr<int>(), f32(err), (float)lr,
+                               (int)reg_type, (float)reg_coef, B, K,
+                               cur_stream());
+}
+
+void lr_ftrl_wide_forward(torch::Tensor zn, torch::Tensor keys,
+                          torch::Tensor vals, torch::Tensor ptr,
+                          torch::Tensor labels,
+                          c10::optional<torch::Tensor> wts, torch::Tensor err,
+                          torch::Tensor loss, double alpha, double beta,
+                          double l1, double l2, int64_t K,
+                          bool labels_checked) {
+  check_f32(zn, "zn"); check_f32(vals, "vals"); check_f32(labels, "labels");
+  check_f32(err, "err"); check_f32(loss, "loss");
+  check_ftrl_wide_k(zn, K);
+  int64_t B = check_csr(keys, vals, ptr);
+  TORCH_CHECK(labels.numel() == B && loss.numel() == B, "batch mismatch");
+  TORCH_CHECK(err.numel() == B * K, "err must be [B, K]");
+  const float* wp = opt_weights(wts, B);
+  check_labels(labels, K, labels_checked);
+  mv_launch_lr_ftrl_wide_fwd(f32(zn), keys.data_ptr<int64_t>(), f32(vals),
+                             ptr.data_ptr<int>(), f32(labels), wp, f32(err),
+                             f32(loss), (float)(1.0 / alpha), (float)beta,
+                             (float)l1, (float)l2, B, K, cur_stream());
+}
+
+void lr_ftrl_wide_scatter(torch::Tensor zn, torch::Tensor keys,
+                          torch::Tensor vals, torch::Tensor ptr,
+                          torch::Tensor err, double alpha, double beta,
+                          double l1, double l2, int64_t K) {
+  check_f32(zn, "zn"); check_f32(vals, "vals"); check_f32(err, "err");
+  check_ftrl_wide_k(zn, K);
+  int64_t B = check_csr(keys, vals, ptr);
+  TORCH_CHECK(err.numel() == B * K, "err must be [B, K]");
+  mv_launch_lr_ftrl_scatter(f32(zn), keys.data_ptr<int64_t>(), f32(vals),
+                            ptr.data_ptr<int>(), f32(err),
+                            (float)(1.0 / alpha), (float)beta, (float)l1,
+                            (float)l2, B, K, cur_stream());
+}
+
+void lr_dense_post_wide(torch::Tensor logits, torch::Tensor labels,
+                        c10::optional<torch::Tensor> wts,
+                        torch::Tensor loss_acc, double inv_b) {
+  check_f32(logits, "logits"); check_f32(labels, "labels");
+  check_f32(loss_acc, "loss_acc");
+  int64_t B = labels.numel();
+  TORCH_CHECK(B > 0 && logits.numel() % B == 0,
+              "logits/labels batch mismatch");
+  int64_t K = logits.numel() / B;
+  TORCH_CHECK(K >= 65 && K <= LR_WIDE_MAX,
+              "wide fused dense post supports 65..1024 classes (got ", K,
+              ")");
+  TORCH_CHECK(loss_acc.numel() == 1, "loss_acc must be a scalar");
+  mv_launch_lr_dense_post_wide(f32(logits), f32(labels), opt_weights(wts, B),
+                               f32(loss_acc), (float)inv_b, B, K,
+                               cur_stream());
+}
+
 // (scores [Q,k] fp32, ids [Q,k] int64, global) of the k nearest shard rows
 // per query, or None when the launcher refuses (the caller takes its next
 // path). Slots past the shard's rows are (-inf, INT64_MAX). The two scans
@@ -819,6 +932,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lr_ftrl_scatter", &lr_ftrl_scatter,
         "FTRL fused z/n state update (updater.cpp:79-101 applied to the "
         "local chunk buffer)");
+  m.def("lr_softmax_wide_forward", &lr_softmax_wide_forward,
+        "K13 softmax fused, class per lane: 65..1024 classes; labels outside "
+        "[0, K) are refused (a sync) unless labels_checked",
+        py::arg("w"), py::arg("keys"), py::arg("vals"), py::arg("ptr"),
+        py::arg("labels"), py::arg("wts"), py::arg("err"), py::arg("loss"),
+        py::arg("K"), py::arg("labels_checked") = false);
+  m.def("lr_softmax_wide_scatter", &lr_softmax_wide_scatter,
+        "K14 softmax fused for 65..1024 classes (k_lr_softmax_scatter)");
+  m.def("lr_ftrl_wide_forward", &lr_ftrl_wide_forward,
+        "FTRL fused forward, class per lane: 33..1024 outputs; labels as in "
+        "lr_softmax_wide_forward",
+        py::arg("zn"), py::arg("keys"), py::arg("vals"), py::arg("ptr"),
+        py::arg("labels"), py::arg("wts"), py::arg("err"), py::arg("loss"),
+        py::arg("alpha"), py::arg("beta"), py::arg("l1"), py::arg("l2"),
+        py::arg("K"), py::arg("labels_checked") = false);
+  m.def("lr_ftrl_wide_scatter", &lr_ftrl_wide_scatter,
+        "FTRL fused z/n state update for 33..1024 outputs "
+        "(k_lr_ftrl_scatter)");
+  m.def("lr_dense_post_wide", &lr_dense_post_wide,
+        "Dense-mode fused post-GEMM for 65..1024 classes: logits -> softmax "
+        "diff in place + atomic mean-loss accumulate");
   m.def("row_scatter_adagrad", &row_scatter_adagrad,
         "K15: keyed adagrad update on owned shard rows "
         "(assume_unique=True uses plain stores)",

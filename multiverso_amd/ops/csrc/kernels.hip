@@ -1397,6 +1397,20 @@ static __device__ __forceinline__ float wave_max(float v) {
   for (int sh = 32; sh; sh >>= 1) v = fmaxf(v, __shfl_xor(v, sh, 64));
   return v;
 }
+// value of lane `src` (wave-uniform) on every lane; the result is scalar
+static __device__ __forceinline__ float lane_bcast(float v, int src) {
+  return __builtin_bit_cast(
+      float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
+}
+static __device__ __forceinline__ int lane_bcast(int v, int src) {
+  return __builtin_amdgcn_readlane(v, src);
+}
+static __device__ __forceinline__ int64_t lane_bcast(int64_t v, int src) {
+  uint32_t lo = (uint32_t)lane_bcast((int)v, src);
+  uint32_t hi = (uint32_t)lane_bcast((int)(v >> 32), src);
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
 template <int K>
 static __device__ __forceinline__ void wave_sum(float (&l)[K]) {
 #pragma unroll
@@ -1973,6 +1987,300 @@ extern "C" int mv_launch_lr_dense_fwd(const float* X, const float* W,
   });
 }
 
+// ---------------------------------------------------------------------------
+// Class-per-lane ("wide") forms of the softmax and FTRL forwards and of the
+// dense post step, for the class counts the kernels above stop at: softmax
+// 65..1024 classes, FTRL 33..1024 outputs, dense post 65..1024 columns.
+//
+// The kernels above put the lanes over a sample's features and keep all K
+// logits in every lane: K registers per lane, a K*4-byte row read per lane,
+// and a butterfly per class. From 64 classes up the opposite split is the
+// natural one. Lane l owns classes l, l+64, ... (CPL = ceil(K/64) logits in
+// registers), a table row is one coalesced wave load per 64 classes, and the
+// dot product needs no cross-lane reduction at all: every class adds its
+// features in CSR order, so the result is repeatable bit for bit.
+//
+// One wave per sample, grid-stride. The sample's CSR segment is staged 64
+// features at a time (lane t loads keys[jb+t] and vals[jb+t] once,
+// coalesced); the wave then walks the staged features, each (key, val) read
+// from its lane into scalar registers, so a row's address is a scalar base
+// plus the lane's class column. wide_nf features' row loads are issued before
+// the first fma of the group. The scatter half of a minibatch is
+// k_lr_softmax_scatter / k_lr_ftrl_scatter, which serve any K already.
+// ---------------------------------------------------------------------------
+
+// the wide kernels use the scalar fp32 forms only, no packed arithmetic (a
+// device target feature; the host pass does not know it)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define WIDE_SCALAR_FP32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define WIDE_SCALAR_FP32
+#endif
+
+// CPL register bucket of a class count: exact up to 4, then the next
+// instantiated bucket (dead registers read a clamped column and are masked
+// in the epilogue, so an oversize CPL costs idle loads only). Beyond 1024
+// classes it returns a CPL with no instantiation, which the launchers trap
+// on; the host refuses before that.
+static int lr_cpl_bucket(int64_t K) {
+  int cpl = (int)((K + 63) / 64);
+  if (cpl > 4) cpl = (cpl <= 6) ? 6 : (cpl <= 8) ? 8 : (cpl <= 12) ? 12
+                   : (cpl <= 16) ? 16 : cpl;
+  return cpl;
+}
+// f(kint<CPL>()) for K's bucket. ONE: the caller's range reaches below 65
+// classes (FTRL's 33..64), so CPL = 1 is instantiated too.
+template <bool ONE, class F>
+static void with_cpl(int64_t K, F f) {
+  int cpl = lr_cpl_bucket(K);
+  if constexpr (ONE)
+    if (cpl == 1) return f(kint<1>());
+  switch (cpl) {
+    case 2: f(kint<2>()); break;
+    case 3: f(kint<3>()); break;
+    case 4: f(kint<4>()); break;
+    case 6: f(kint<6>()); break;
+    case 8: f(kint<8>()); break;
+    case 12: f(kint<12>()); break;
+    case 16: f(kint<16>()); break;
+    default: __builtin_trap();  // K > 1024: host refuses before launch
+  }
+}
+
+// Features whose row loads a wave keeps in flight, by the loads one feature
+// takes (CPL for softmax, 2*CPL for FTRL's z and n). Up to 4 loads a feature,
+// 16 loads in flight pay: 21 us for 28 at softmax K = 100, 43 us for 56 at
+// FTRL K = 100. From 6 loads a feature on, one feature at a time is as fast
+// or faster (50 us for 52.5 at softmax K = 300, level at K = 1000): eight
+// waves a SIMD already cover the latency. Timed on a 4096 x 64 minibatch,
+// profiles/lr_wide.md.
+constexpr int wide_nf(int loads_per_feature) {
+  return loads_per_feature <= 4 ? 16 / loads_per_feature : 1;
+}
+
+// The column of this lane's r-th class, lane + 64 r, clamped to K - 1: every
+// load through it is unconditional and in bounds, and what a dead class
+// (>= K) reads is dropped by the select on the value in the epilogues.
+template <int CPL>
+static __device__ __forceinline__ void wide_cols(int (&col)[CPL], int lane,
+                                                 int K) {
+#pragma unroll
+  for (int r = 0; r < CPL; ++r) {
+    int cls = lane + 64 * r;
+    col[r] = cls < K ? cls : K - 1;
+  }
+}
+
+// N staged features, f .. f+N-1 of the round held in (key, val) across the
+// lanes: l[r] += val * term(the NV values of class col[r] in the feature's
+// row), a row being NV runs of K floats. All N * CPL * NV loads are issued
+// before the first term is evaluated.
+template <int CPL, int NV, int N, class Term>
+static __device__ __forceinline__ void wide_add(
+    float (&l)[CPL], const float* __restrict__ table, int K,
+    const int (&col)[CPL], int64_t key, float val, int f, Term term) {
+  float v[N], raw[N][CPL][NV];
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const float* row = table + lane_bcast(key, f + u) * (int64_t)(NV * K);
+    v[u] = lane_bcast(val, f + u);
+#pragma unroll
+    for (int r = 0; r < CPL; ++r)
+#pragma unroll
+      for (int q = 0; q < NV; ++q) raw[u][r][q] = row[q * K + col[r]];
+  }
+#pragma unroll
+  for (int u = 0; u < N; ++u)
+#pragma unroll
+    for (int r = 0; r < CPL; ++r) l[r] += v[u] * term(raw[u][r]);
+}
+
+// The CSR walk of one sample, features [jb, je): rounds of 64 staged
+// features, each walked NF at a time and then one at a time. The staging
+// index is clamped like the columns; a lane past the end is never read from.
+template <int CPL, int NV, int NF, class Term>
+static __device__ __forceinline__ void wide_logits(
+    float (&l)[CPL], const float* __restrict__ table,
+    const int64_t* __restrict__ keys, const float* __restrict__ vals, int jb,
+    int je, int K, int lane, const int (&col)[CPL], Term term) {
+  for (int sb = jb; sb < je; sb += 64) {
+    int cnt = je - sb < 64 ? je - sb : 64;
+    int j = sb + lane < je ? sb + lane : je - 1;
+    int64_t key = keys[j];
+    float val = vals[j];
+    int f = 0;
+    for (; f + NF <= cnt; f += NF)
+      wide_add<CPL, NV, NF>(l, table, K, col, key, val, f, term);
+    for (; f < cnt; ++f)
+      wide_add<CPL, NV, 1>(l, table, K, col, key, val, f, term);
+  }
+}
+
+// Softmax of sample i over the K logits l[r] of class lane + 64 r. Writes
+// (p_k - [k == y]) * wt to out[k] for the K classes, coalesced, and returns
+// the sample's loss -log(p_y + eps) on every lane; p_y comes from lane
+// y & 63, register y >> 6, by an unrolled select (no dynamic indexing). Label
+// and weight are read after the reductions, as in softmax_epilogue.
+template <int CPL>
+static __device__ __forceinline__ float wide_softmax_epilogue(
+    float (&l)[CPL], int K, int lane, int i, const float* labels,
+    const float* wts, float* out) {
+  float mx = -1e30f;
+#pragma unroll
+  for (int r = 0; r < CPL; ++r) {
+    l[r] = (lane + 64 * r < K) ? l[r] : -1e30f;
+    mx = fmaxf(mx, l[r]);
+  }
+  mx = wave_max(mx);
+  float se = 0.f;
+#pragma unroll
+  for (int r = 0; r < CPL; ++r) {
+    l[r] = (lane + 64 * r < K) ? expf(l[r] - mx) : 0.f;
+    se += l[r];
+  }
+  se = wave_sum(se);
+  int y = (int)labels[i];
+  float wt = weight_of(wts, i);
+  float mine = 0.f;
+#pragma unroll
+  for (int r = 0; r < CPL; ++r) {
+    int cls = lane + 64 * r;
+    float p = l[r] / se;
+    if (cls < K) out[cls] = (p - (cls == y)) * wt;
+    if ((y >> 6) == r) mine = p;
+  }
+  float py = __shfl(mine, y & 63, 64);
+  return -logf(py + LR_LOG_EPS);
+}
+
+template <int CPL, int NF>
+__global__ __launch_bounds__(BLOCK) WIDE_SCALAR_FP32 void
+k_lr_softmax_wide_fwd(
+    const float* __restrict__ w, const int64_t* __restrict__ keys,
+    const float* __restrict__ vals, const int* __restrict__ ptr,
+    const float* __restrict__ labels, const float* __restrict__ wts,
+    float* __restrict__ err, float* __restrict__ loss, int B, int K) {
+  const Wave wv = this_wave(BLOCK);
+  int col[CPL];
+  wide_cols(col, wv.lane, K);
+  for (int i = wv.id; i < B; i += wv.n) {
+    float l[CPL] = {};
+    wide_logits<CPL, 1, NF>(l, w, keys, vals, ptr[i], ptr[i + 1], K, wv.lane,
+                            col, [](const float (&x)[1]) { return x[0]; });
+    float ll = wide_softmax_epilogue(l, K, wv.lane, i, labels, wts,
+                                     err + (int64_t)i * K);
+    if (wv.lane == 0) loss[i] = ll;
+  }
+}
+
+// FTRL: the same walk over (z | n) rows of 2K floats, the term being the
+// weight ftrl_w reconstructs; then a sigmoid per output against
+// [cls == label] and the binary NLL summed over all K outputs (registers,
+// then the wave), as k_lr_ftrl_fwd and Objective.loss have it.
+template <int CPL, int NF>
+__global__ __launch_bounds__(BLOCK) WIDE_SCALAR_FP32 void
+k_lr_ftrl_wide_fwd(
+    const float* __restrict__ zn, const int64_t* __restrict__ keys,
+    const float* __restrict__ vals, const int* __restrict__ ptr,
+    const float* __restrict__ labels, const float* __restrict__ wts,
+    float* __restrict__ err, float* __restrict__ loss, float alpha_inv,
+    float beta, float l1, float l2, int B, int K) {
+  const Wave wv = this_wave(BLOCK);
+  int col[CPL];
+  wide_cols(col, wv.lane, K);
+  for (int i = wv.id; i < B; i += wv.n) {
+    float l[CPL] = {};
+    wide_logits<CPL, 2, NF>(l, zn, keys, vals, ptr[i], ptr[i + 1], K, wv.lane,
+                            col, [&](const float (&x)[2]) {
+                              return ftrl_w(x[0], x[1], alpha_inv, beta, l1,
+                                            l2);
+                            });
+    int y = (int)labels[i];
+    float wt = weight_of(wts, i);
+    float* out = err + (int64_t)i * K;
+    float ll = 0.f;
+#pragma unroll
+    for (int r = 0; r < CPL; ++r) {
+      int cls = wv.lane + 64 * r;
+      float p = 1.f / (1.f + expf(-l[r]));
+      float yk = (float)(cls == y);
+      float nll = -(yk * logf(p + LR_LOG_EPS) +
+                    (1.f - yk) * logf(1.f - p + LR_LOG_EPS));
+      if (cls < K) out[cls] = (p - yk) * wt;
+      ll += (cls < K) ? nll : 0.f;
+    }
+    ll = wave_sum(ll);
+    if (wv.lane == 0) loss[i] = ll;
+  }
+}
+
+// The in-place post-GEMM step of k_lr_dense_post for 65..1024 columns: one
+// wave per sample reads its logits row lane-strided, runs the wide epilogue
+// into the same row (every read of the row precedes the reductions, every
+// write follows them) and accumulates the mean loss the same way.
+template <int CPL>
+__global__ __launch_bounds__(BLOCK) WIDE_SCALAR_FP32 void
+k_lr_dense_post_wide(
+    float* __restrict__ logits, const float* __restrict__ labels,
+    const float* __restrict__ wts, float* __restrict__ loss_acc, float inv_b,
+    int B, int K) {
+  float* block_loss = block_loss_begin();
+  const Wave wv = this_wave(BLOCK);
+  int col[CPL];
+  wide_cols(col, wv.lane, K);
+  float ll_sum = 0.f;
+  for (int i = wv.id; i < B; i += wv.n) {
+    float* row = logits + (int64_t)i * K;
+    float l[CPL];
+#pragma unroll
+    for (int r = 0; r < CPL; ++r) l[r] = row[col[r]];
+    float t = wide_softmax_epilogue(l, K, wv.lane, i, labels, wts, row);
+    if (wv.lane == 0) ll_sum += t;
+  }
+  block_loss_end(block_loss, loss_acc, inv_b, wv.lane, ll_sum);
+}
+
+extern "C" void mv_launch_lr_softmax_wide_fwd(
+    const float* w, const int64_t* keys, const float* vals, const int* ptr,
+    const float* labels, const float* wts, float* err, float* loss,
+    int64_t B, int64_t K, hipStream_t s) {
+  if (!B) return;
+  with_cpl<false>(K, [&](auto c) {
+    constexpr int CPL = decltype(c)::value;
+    k_lr_softmax_wide_fwd<CPL, wide_nf(CPL)>
+        <<<grid_for(B * 64), BLOCK, 0, s>>>(w, keys, vals, ptr, labels, wts,
+                                            err, loss, (int)B, (int)K);
+  });
+}
+
+extern "C" void mv_launch_lr_ftrl_wide_fwd(
+    const float* zn, const int64_t* keys, const float* vals, const int* ptr,
+    const float* labels, const float* wts, float* err, float* loss,
+    float alpha_inv, float beta, float l1, float l2, int64_t B, int64_t K,
+    hipStream_t s) {
+  if (!B) return;
+  with_cpl<true>(K, [&](auto c) {
+    constexpr int CPL = decltype(c)::value;
+    k_lr_ftrl_wide_fwd<CPL, wide_nf(2 * CPL)>
+        <<<grid_for(B * 64), BLOCK, 0, s>>>(zn, keys, vals, ptr, labels, wts,
+                                            err, loss, alpha_inv, beta, l1,
+                                            l2, (int)B, (int)K);
+  });
+}
+
+extern "C" void mv_launch_lr_dense_post_wide(float* logits,
+                                             const float* labels,
+                                             const float* wts,
+                                             float* loss_acc, float inv_b,
+                                             int64_t B, int64_t K,
+                                             hipStream_t s) {
+  if (!B) return;
+  with_cpl<false>(K, [&](auto c) {
+    k_lr_dense_post_wide<decltype(c)::value>
+        <<<grid_for_cap(B * 64, 512), BLOCK, 0, s>>>(
+            logits, labels, wts, loss_acc, inv_b, (int)B, (int)K);
+  });
+}
 
 // ---------------------------------------------------------------------------
 // Nearest rows (MatrixTable.nearest_rows): the k best rows of the shard for
@@ -2016,15 +2324,6 @@ extern "C" int mv_launch_lr_dense_fwd(const float* X, const float* W,
 static __device__ __forceinline__ bool topk_before(float sa, int ia, float sb,
                                                    int ib) {
   return sa > sb || (sa == sb && ia < ib);
-}
-
-// value of lane `src` (wave-uniform) on every lane
-static __device__ __forceinline__ float lane_bcast(float v, int src) {
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
-}
-static __device__ __forceinline__ int lane_bcast(int v, int src) {
-  return __builtin_amdgcn_readlane(v, src);
 }
 
 // Offers (s, id), the same on all 64 lanes, to the sorted list whose j-th

@@ -102,6 +102,20 @@ void mv_launch_lr_ftrl_fwd(const float*, const int64_t*, const float*,
 void mv_launch_lr_ftrl_scatter(float*, const int64_t*, const float*,
                                const int*, const float*, float, float,
                                float, float, int64_t, int64_t, hipStream_t);
+// class-per-lane forwards, same arguments as the two forwards above: softmax
+// for 65..1024 classes, FTRL for 33..1024 outputs (the scatters above serve
+// any K)
+void mv_launch_lr_softmax_wide_fwd(const float*, const int64_t*, const float*,
+                                   const int*, const float*, const float*,
+                                   float*, float*, int64_t, int64_t,
+                                   hipStream_t);
+void mv_launch_lr_ftrl_wide_fwd(const float*, const int64_t*, const float*,
+                                const int*, const float*, const float*,
+                                float*, float*, float, float, float, float,
+                                int64_t, int64_t, hipStream_t);
+// dense post for 65..1024 columns, same arguments as mv_launch_lr_dense_post
+void mv_launch_lr_dense_post_wide(float*, const float*, const float*, float*,
+                                  float, int64_t, int64_t, hipStream_t);
 // dense logreg: post (logits, labels, wts-or-null, loss_acc, inv_b, B, K);
 // fwd (X, W, labels, wts-or-null, diff, loss_acc, inv_b, B, d, K, nt),
 // which returns 0 when the caller has to take the GEMM + post path
