@@ -286,6 +286,49 @@ void onebit_decode_sum(torch::Tensor out, torch::Tensor payloads,
                               (int)nparts, n, cur_stream());
 }
 
+// Block top-k Add wire (topk_filter.py): keep (value, position) pairs per
+// block of 1024 elements, 6 bytes a pair
+int64_t topk_bytes(int64_t n, int64_t keep) {
+  return 6 * keep * ((n + 1023) / 1024);
+}
+
+void check_keep(int64_t keep) {
+  TORCH_CHECK(keep >= 4 && keep <= 256 && keep % 4 == 0,
+              "keep must be a multiple of 4 in 4..256, got ", keep);
+}
+
+// payload <- the keep largest-magnitude entries per block of (residual +
+// delta); residual <- +0 where sent, the sum elsewhere. delta and residual
+// may be 4-byte-aligned views (pieces of a table).
+void topk_encode(torch::Tensor delta, torch::Tensor residual,
+                 torch::Tensor payload, int64_t keep) {
+  int64_t n = check_same({{"delta", delta}, {"residual", residual}});
+  TORCH_CHECK(n >= 1, "topk_encode: empty piece");
+  TORCH_CHECK((n + 1023) / 1024 <= INT32_MAX, "topk_encode: piece too large");
+  check_keep(keep);
+  check_payload(payload, "payload", topk_bytes(n, keep));
+  mv_launch_topk_encode(f32(delta), f32(residual),
+                        payload.data_ptr<uint8_t>(), n, (int)keep,
+                        cur_stream());
+}
+
+// out <- the sum, in payload order, of what nparts consecutive payloads of
+// one n-element piece hold for each element
+void topk_decode_sum(torch::Tensor out, torch::Tensor payloads,
+                     int64_t nparts, int64_t keep) {
+  check_f32(out, "out");
+  int64_t n = out.numel();
+  TORCH_CHECK(n >= 1, "topk_decode_sum: empty piece");
+  TORCH_CHECK((n + 1023) / 1024 <= INT32_MAX,
+              "topk_decode_sum: piece too large");
+  TORCH_CHECK(nparts >= 1 && nparts <= INT32_MAX,
+              "topk_decode_sum: nparts must be >= 1");
+  check_keep(keep);
+  check_payload(payloads, "payloads", nparts * topk_bytes(n, keep));
+  mv_launch_topk_decode_sum(f32(out), payloads.data_ptr<uint8_t>(),
+                            (int)nparts, n, (int)keep, cur_stream());
+}
+
 void row_gather_out(torch::Tensor out, torch::Tensor shard, torch::Tensor rows) {
   check_f32(shard, "shard");
   TORCH_CHECK(shard.dim() == 2, "shard must be 2-D");
@@ -898,6 +941,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("onebit_decode_sum", &onebit_decode_sum,
         "1-bit wire: out = sum over nparts payloads of their decoded values",
         py::arg("out"), py::arg("payloads"), py::arg("nparts"));
+  m.def("topk_encode", &topk_encode,
+        "top-k wire: payload = the keep largest |residual + delta| per block "
+        "of 1024 as (value, position) pairs, residual = what stays behind",
+        py::arg("delta"), py::arg("residual"), py::arg("payload"),
+        py::arg("keep"));
+  m.def("topk_decode_sum", &topk_decode_sum,
+        "top-k wire: out = sum over nparts payloads of the pairs they hold",
+        py::arg("out"), py::arg("payloads"), py::arg("nparts"),
+        py::arg("keep"));
   m.def("row_gather", &row_gather,
         "K6: out[i] = shard[rows[i]]; dtype=torch.bfloat16 narrows",
         py::arg("shard"), py::arg("rows"), py::arg("dtype") = py::none());

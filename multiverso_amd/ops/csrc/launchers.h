@@ -48,6 +48,11 @@ void mv_launch_onebit_encode(const float*, float*, uint8_t*, int64_t,
                              hipStream_t);
 void mv_launch_onebit_decode_sum(float*, const uint8_t*, int, int64_t,
                                  hipStream_t);
+// top-k wire: (..., n, keep)
+void mv_launch_topk_encode(const float*, float*, uint8_t*, int64_t, int,
+                           hipStream_t);
+void mv_launch_topk_decode_sum(float*, const uint8_t*, int, int64_t, int,
+                               hipStream_t);
 void mv_launch_row_gather(void*, int, const float*, const int64_t*, int64_t,
                           int64_t, hipStream_t);
 void mv_launch_row_scatter_add(float*, const void*, int, const int64_t*, float,

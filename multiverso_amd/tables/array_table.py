@@ -19,7 +19,10 @@ shard, updater state and Store/Load stay fp32.
 ``add_filter="onebit"`` (float32 tables) sends every whole-table Add through
 onebit_filter: signs plus two scales per 1024 elements, the quantisation
 error kept in ``self.residual`` (fp32, the full table size, per worker) and
-added to the next delta. Get, Store and Load are unfiltered.
+added to the next delta. ``add_filter="topk"`` / ``"topk:M"`` sends only the M
+largest-magnitude entries per 1024 elements (32 by default), as exact fp32,
+through topk_filter, with the same residual. Get, Store and Load are
+unfiltered.
 """
 
 from __future__ import annotations

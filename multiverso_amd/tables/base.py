@@ -55,6 +55,7 @@ class Table:
         # (_set_add_filter)
         self.add_filter: Optional[str] = None
         self.residual: Optional[torch.Tensor] = None
+        self._codec = None
         # async mode: a fast worker's request can arrive before THIS
         # rank finished constructing the table (the reference's
         # RegisterTable round-trip subsumed this); the server thread
@@ -94,8 +95,15 @@ class Table:
                         wire_dtype: Optional[torch.dtype]) -> None:
         """Resolve the ``add_filter`` keyword: None sends whole-table deltas
         as they are; "onebit" sends them through onebit_filter (1 bit per
-        element plus two fp32 scales per 1024, error feedback), on both
-        planes and on a single rank alike. float32 tables only.
+        element plus two fp32 scales per 1024), "topk" or "topk:M" through
+        topk_filter (the M largest-magnitude entries per 1024 as exact fp32,
+        M = 32 by default); both with error feedback, on both planes and on
+        a single rank alike. float32 tables only.
+
+        ``self._codec`` is what encodes and decodes the table's Adds
+        (``payload_bytes(n)``, ``encode(piece, res, out=None)``,
+        ``decode_sum(payloads, n, nparts, out=None)``): the onebit_filter
+        module, or a topk_filter.Codec bound to M.
 
         ``self.residual`` is the error-feedback state: fp32, the table's
         FULL flat size (not this rank's shard: a worker quantises the whole
@@ -104,18 +112,33 @@ class Table:
         Like updater state it is not written by ``store`` or checkpoints."""
         self.add_filter = add_filter
         self.residual: Optional[torch.Tensor] = None
+        self._codec = None
         if add_filter is None:
             return
-        if add_filter != "onebit":
+        name, colon, arg = str(add_filter).partition(":")
+        if name == "onebit" and not colon:
+            from .. import onebit_filter
+            self._codec = onebit_filter
+        elif name == "topk":
+            from .. import topk_filter
+            if colon and not arg.isdecimal():
+                raise ValueError(f"add_filter {add_filter!r}: what follows "
+                                 f"'topk:' must be a number")
+            try:
+                self._codec = topk_filter.Codec(int(arg) if colon
+                                                else topk_filter.DEFAULT_KEEP)
+            except ValueError as e:
+                raise ValueError(f"add_filter {add_filter!r}: {e}") from None
+        else:
             raise ValueError(f"add_filter {add_filter!r} is not known "
-                             f"(None or 'onebit')")
+                             f"(None, 'onebit', 'topk' or 'topk:M')")
         if dtype != torch.float32:
-            raise TypeError(f"add_filter='onebit' needs a float32 table, "
-                            f"not {dtype}")
+            raise TypeError(f"add_filter={add_filter!r} needs a float32 "
+                            f"table, not {dtype}")
         if wire_dtype == torch.bfloat16:
-            raise TypeError("add_filter='onebit' together with "
+            raise TypeError(f"add_filter={add_filter!r} together with "
                             "wire_dtype=torch.bfloat16 is not supported yet "
-                            "(a follow-up: bf16 Get under a 1-bit Add)")
+                            "(a follow-up: bf16 Get under a filtered Add)")
 
     def _filter_residual(self, numel: int) -> torch.Tensor:
         if self.residual is None:
@@ -127,10 +150,9 @@ class Table:
         """Single rank: what the owner would decode from this delta, as a
         fresh fp32 tensor of the table's own (the semantics do not depend on
         the world size, as the bf16 wire still rounds on one rank)."""
-        from .. import onebit_filter
-        payload = onebit_filter.encode(
+        payload = self._codec.encode(
             delta, self._filter_residual(delta.numel()))
-        return onebit_filter.decode_sum(payload, delta.numel(), 1)
+        return self._codec.decode_sum(payload, delta.numel(), 1)
 
     def _stage_get(self, out: torch.Tensor) -> bool:
         """bf16 wire only: a Get buffer of another dtype (fp32, say) is

@@ -165,7 +165,7 @@ class DenseTable(Table):
             if self.add_filter and self.zoo.size > 1:
                 chunk, h = onebit_exchange_delta(
                     delta, self._filter_residual(delta.numel()), self.spec,
-                    self._cols, async_op=async_op)
+                    self._cols, async_op=async_op, codec=self._codec)
             else:
                 chunk, h = reduce_scatter_delta(delta, self.spec, self._cols,
                                                 async_op=async_op)

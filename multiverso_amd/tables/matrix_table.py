@@ -33,8 +33,11 @@ MI355X mapping:
 - ``add_filter="onebit"`` (float32 tables): every whole-table Add goes
   through onebit_filter — signs plus two scales per 1024 elements, the
   quantisation error kept in ``self.residual`` (fp32, the full table size,
-  per worker) and added to the next delta. Row-keyed ops, Get, Store and
-  Load are unfiltered and leave the residual alone.
+  per worker) and added to the next delta. ``add_filter="topk"`` /
+  ``"topk:M"`` goes through topk_filter instead: the M largest-magnitude
+  entries per 1024 elements (32 by default) as exact fp32, the same residual.
+  Row-keyed ops, Get, Store and Load are unfiltered and leave the residual
+  alone.
 
 - ``nearest_rows`` = top-k row search where the shard lives: each owner scans
   its rows once (k_row_topk, from 17 queries k_row_topk_mm, + k_topk_merge)
