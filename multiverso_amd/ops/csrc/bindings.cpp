@@ -353,6 +353,76 @@ torch::Tensor row_gather(torch::Tensor shard, torch::Tensor rows,
   return out;
 }
 
+// out[rows[i]] = shard[rows[i]]: out has the shard's shape, rows are unique
+void row_gather_at(torch::Tensor out, torch::Tensor shard,
+                   torch::Tensor rows) {
+  check_f32(shard, "shard");
+  check_f32(out, "out");
+  TORCH_CHECK(shard.dim() == 2 && out.dim() == 2, "out and shard must be 2-D");
+  TORCH_CHECK(out.size(1) == shard.size(1), "out column count mismatch");
+  TORCH_CHECK(rows.scalar_type() == torch::kInt64 && rows.is_cuda() &&
+              rows.is_contiguous(), "rows must be contiguous int64 on GPU");
+  mv_launch_row_gather_at(f32(out), f32(shard), rows.data_ptr<int64_t>(),
+                          rows.numel(), shard.size(1), cur_stream());
+}
+
+// Stale-row lists of SparseMatrixTable: bitmap [workers, R] of bytes, 0 =
+// stale. Returns the row count R; the worker range is [w0, w1).
+int64_t check_bitmap(const torch::Tensor& bitmap, int64_t w0, int64_t w1) {
+  TORCH_CHECK(bitmap.is_cuda(), "bitmap must be on GPU");
+  TORCH_CHECK(bitmap.scalar_type() == torch::kBool ||
+              bitmap.scalar_type() == torch::kUInt8,
+              "bitmap must be bool or uint8");
+  TORCH_CHECK(bitmap.dim() == 2 && bitmap.is_contiguous(),
+              "bitmap must be a contiguous [workers, rows] tensor");
+  TORCH_CHECK(0 <= w0 && w0 <= w1 && w1 <= bitmap.size(0),
+              "worker range [", w0, ", ", w1, ") outside the bitmap's ",
+              bitmap.size(0), " workers");
+  TORCH_CHECK(w1 - w0 <= 65535, "at most 65535 workers per call");
+  TORCH_CHECK(bitmap.size(1) <= INT32_MAX, "bitmap rows must be below 2^31");
+  return bitmap.size(1);
+}
+
+// (plan, totals): totals[w - w0] = the stale rows of worker w, on the CPU (the
+// operation's one device-to-host copy); plan is what stale_emit needs, over
+// the same bitmap, unchanged.
+std::tuple<torch::Tensor, torch::Tensor> stale_count(torch::Tensor bitmap,
+                                                     int64_t w0, int64_t w1) {
+  int64_t R = check_bitmap(bitmap, w0, w1), nw = w1 - w0;
+  auto i64 = bitmap.options().dtype(torch::kInt64);
+  if (R == 0 || nw == 0)
+    return {torch::empty({0}, i64),
+            torch::zeros({nw}, torch::dtype(torch::kInt64))};
+  int64_t n = nw * mv_stale_tiles(R);
+  auto tile_count = torch::empty({n}, i64.dtype(torch::kInt32));
+  auto plan = torch::empty({n + nw + 1}, i64);
+  mv_launch_stale_count((const uint8_t*)bitmap.data_ptr(), R, (int)w0,
+                        (int)nw, tile_count.data_ptr<int32_t>(),
+                        plan.data_ptr<int64_t>(), cur_stream());
+  return {plan, plan.narrow(0, n, nw).cpu()};
+}
+
+// ids [n]: the local ids of the stale rows of workers [w0, w1), worker-major
+// and ascending inside a worker; n = the sum of stale_count's totals. The
+// listed rows become fresh.
+torch::Tensor stale_emit(torch::Tensor bitmap, torch::Tensor plan, int64_t w0,
+                         int64_t w1, int64_t n) {
+  int64_t R = check_bitmap(bitmap, w0, w1), nw = w1 - w0;
+  TORCH_CHECK(n >= 0, "stale_emit: negative n");
+  auto ids = torch::empty({n}, bitmap.options().dtype(torch::kInt64));
+  if (n == 0 || R == 0 || nw == 0) {
+    TORCH_CHECK(n == 0, "stale_emit: n rows of an empty range");
+    return ids;
+  }
+  check_dev(plan, "plan", torch::kInt64);
+  TORCH_CHECK(plan.numel() == nw * mv_stale_tiles(R) + nw + 1,
+              "plan does not belong to this bitmap and range");
+  mv_launch_stale_emit((uint8_t*)bitmap.data_ptr(), R, (int)w0, (int)nw,
+                       plan.data_ptr<int64_t>(), ids.data_ptr<int64_t>(), n,
+                       cur_stream());
+  return ids;
+}
+
 void row_scatter_add(torch::Tensor shard, torch::Tensor rows,
                      torch::Tensor vals, double sign,
                      bool assume_unique = false) {
@@ -954,6 +1024,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K6: out[i] = shard[rows[i]]; dtype=torch.bfloat16 narrows",
         py::arg("shard"), py::arg("rows"), py::arg("dtype") = py::none());
   m.def("row_gather_out", &row_gather_out, "K6 (preallocated out)");
+  m.def("row_gather_at", &row_gather_at,
+        "K6 in place: out[rows[i]] = shard[rows[i]], unique rows",
+        py::arg("out"), py::arg("shard"), py::arg("rows"));
+  m.def("stale_count", &stale_count,
+        "stale rows per worker in [w0, w1) of a byte bitmap [workers, rows] "
+        "(0 = stale): (plan for stale_emit, CPU int64 totals)",
+        py::arg("bitmap"), py::arg("w0"), py::arg("w1"));
+  m.def("stale_emit", &stale_emit,
+        "the n stale local row ids of workers [w0, w1), worker-major and "
+        "ascending; marks them fresh",
+        py::arg("bitmap"), py::arg("plan"), py::arg("w0"), py::arg("w1"),
+        py::arg("n"));
   m.def("row_scatter_add", &row_scatter_add,
         "K5: shard[rows[i]] += sign*vals[i] (atomic; assume_unique=True "
         "uses plain stores)", py::arg("shard"), py::arg("rows"),

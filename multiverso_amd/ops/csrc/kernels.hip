@@ -611,7 +611,9 @@ void mv_launch_adam_f64(double* d, double* m, double* v, const double* x,
 
 // V = float, float2 or float4 column groups; total and cols count V's. O is
 // out's element type: float, or bf16 (each group narrowed as it is stored).
-template <class V, class O, class Idx>
+// AT is the destination-indexed form, out[rows[i]] = shard[rows[i]]: out has
+// the shard's shape and the rows are unique (fp32 only).
+template <class V, class O, class Idx, bool AT = false>
 __global__ void k_row_gather(O* __restrict__ out, const V* __restrict__ shard,
                              const int64_t* __restrict__ rows,
                              Idx total, Idx cols) {
@@ -619,8 +621,10 @@ __global__ void k_row_gather(O* __restrict__ out, const V* __restrict__ shard,
   for (Idx i = (Idx)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += stride) {
     Idx r = i / cols, c = i - r * cols;
-    V v = shard[rows[r] * (int64_t)cols + c];
-    if constexpr (std::is_same<O, bf16>::value) st(out, i, v);
+    int64_t at = rows[r] * (int64_t)cols + c;
+    V v = shard[at];
+    if constexpr (AT) ((V*)out)[at] = v;
+    else if constexpr (std::is_same<O, bf16>::value) st(out, i, v);
     else ((V*)out)[i] = v;
   }
 }
@@ -747,30 +751,35 @@ static void launch_row_update(const Op& op, bool vec, const D* vals,
 
 // Column groups of 4, 2 or 1 by cols; a bf16 out also needs the group's
 // store alignment (8 or 4 bytes), an fp32 out is a 16-byte torch allocation.
-template <class O>
+// AT: out is the caller's own buffer, so its alignment is looked at as well.
+template <bool AT = false, class O>
 static void launch_row_gather(O* out, const float* shard, const int64_t* rows,
                               int64_t nrows, int64_t cols, hipStream_t s) {
   if (!nrows || !cols) return;
   int64_t total = nrows * cols;
   constexpr bool narrow_out = std::is_same<O, bf16>::value;
-  bool g4 = cols % 4 == 0 && (!narrow_out || ((uintptr_t)out & 7) == 0);
-  bool g2 = cols % 2 == 0 && (!narrow_out || ((uintptr_t)out & 3) == 0);
+  bool g4 = cols % 4 == 0 && (!narrow_out || ((uintptr_t)out & 7) == 0) &&
+            (!AT || aligned16(out));
+  bool g2 = cols % 2 == 0 && (!narrow_out || ((uintptr_t)out & 3) == 0) &&
+            (!AT || ((uintptr_t)out & 7) == 0);
   if (g4 && total / 4 <= UINT32_MAX) {
-    k_row_gather<float4, O, uint32_t><<<grid_for(total / 4), BLOCK, 0, s>>>(
-        out, (const float4*)shard, rows, (uint32_t)(total / 4),
-        (uint32_t)(cols / 4));
+    k_row_gather<float4, O, uint32_t, AT>
+        <<<grid_for(total / 4), BLOCK, 0, s>>>(
+            out, (const float4*)shard, rows, (uint32_t)(total / 4),
+            (uint32_t)(cols / 4));
   } else if (g4) {
-    k_row_gather<float4, O, int64_t><<<grid_for(total / 4), BLOCK, 0, s>>>(
+    k_row_gather<float4, O, int64_t, AT><<<grid_for(total / 4), BLOCK, 0, s>>>(
         out, (const float4*)shard, rows, total / 4, cols / 4);
   } else if (g2 && total / 2 <= UINT32_MAX) {
-    k_row_gather<float2, O, uint32_t><<<grid_for(total / 2), BLOCK, 0, s>>>(
-        out, (const float2*)shard, rows, (uint32_t)(total / 2),
-        (uint32_t)(cols / 2));
+    k_row_gather<float2, O, uint32_t, AT>
+        <<<grid_for(total / 2), BLOCK, 0, s>>>(
+            out, (const float2*)shard, rows, (uint32_t)(total / 2),
+            (uint32_t)(cols / 2));
   } else if (total <= UINT32_MAX) {
-    k_row_gather<float, O, uint32_t><<<grid_for(total), BLOCK, 0, s>>>(
+    k_row_gather<float, O, uint32_t, AT><<<grid_for(total), BLOCK, 0, s>>>(
         out, shard, rows, (uint32_t)total, (uint32_t)cols);
   } else {
-    k_row_gather<float, O, int64_t><<<grid_for(total), BLOCK, 0, s>>>(
+    k_row_gather<float, O, int64_t, AT><<<grid_for(total), BLOCK, 0, s>>>(
         out, shard, rows, total, cols);
   }
 }
@@ -884,6 +893,12 @@ void mv_launch_row_gather(void* out, int wire, const float* shard,
   with_wire(wire, nullptr, out, [&](auto*, auto* o) {
     launch_row_gather(o, shard, rows, nrows, cols, s);
   });
+}
+
+void mv_launch_row_gather_at(float* out, const float* shard,
+                             const int64_t* rows, int64_t nrows, int64_t cols,
+                             hipStream_t s) {
+  launch_row_gather<true>(out, shard, rows, nrows, cols, s);
 }
 
 void mv_launch_row_scatter_add(float* shard, const void* vals, int wire,
@@ -1112,6 +1127,24 @@ static __device__ __forceinline__ int lanes_below(unsigned long long ballot,
   return __popcll(ballot & ((1ull << lane) - 1ull));
 }
 
+// Inclusive prefix sum of c over the workgroup's threads, in thread order:
+// shuffles inside a wave, then the waves before this one from the LDS table
+// s_wave (one entry per wave). All threads call this; it holds one barrier,
+// and the caller puts another before s_wave is written again.
+static __device__ __forceinline__ int block_scan(int c, int* s_wave, int lane,
+                                                 int wave) {
+  int incl = c;
+#pragma unroll
+  for (int o = 1; o < WAVE; o <<= 1) {
+    int up = __shfl_up(incl, o, WAVE);
+    if (lane >= o) incl += up;
+  }
+  if (lane == WAVE - 1) s_wave[wave] = incl;
+  __syncthreads();
+  for (int w = 0; w < wave; ++w) incl += s_wave[w];
+  return incl;
+}
+
 // Exclusive prefix, in index order, of `flag` over the block's 1024 elements
 // (thread t holds elements t + 256*j). Index order is (round j, wave, lane),
 // so group 4*j + wave's ballot gives the rank inside the group and a 16-entry
@@ -1215,15 +1248,7 @@ __global__ __launch_bounds__(BLOCK) NO_PK_F32 void k_topk_encode(
       // bin 255-t; the thread clears its bin for the next pass
       const int c = s_hist[255 - tid];
       s_hist[255 - tid] = 0;
-      int incl = c;
-#pragma unroll
-      for (int o = 1; o < WAVE; o <<= 1) {
-        int up = __shfl_up(incl, o, WAVE);
-        if (lane >= o) incl += up;
-      }
-      if (lane == WAVE - 1) s_wave[wave] = incl;
-      __syncthreads();
-      for (int w = 0; w < wave; ++w) incl += s_wave[w];
+      const int incl = block_scan(c, s_wave, lane, wave);
       const int above = incl - c;     // elements in the bins above this one
       if (above < need && need <= incl) {   // exactly one thread
         s_pick[0] = 255 - tid;
@@ -1324,6 +1349,165 @@ void mv_launch_topk_decode_sum(float* out, const uint8_t* payloads, int P,
   else
     k_topk_decode_sum<false><<<(unsigned)nb, BLOCK, 0, s>>>(
         out, payloads, stride, P, n, nb, m);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Stale-row lists of SparseMatrixTable (tables/sparse_matrix.py; the
+// reference's UpdateGetState, sparse_matrix_table.cpp:226-258). The owner
+// keeps a byte bitmap up_to_date[num_workers, R]: 0 = the row is stale for
+// that worker, non-zero = fresh. A Get takes, for the workers [w0, w1), the
+// local ids of the stale rows, ascending inside a worker and the workers in
+// order, and marks those rows fresh: one ordered stream compaction, in three
+// launches for all workers together (count per tile, scan of the tile counts,
+// emit), with no global atomics: the same bitmap gives the same list.
+//
+// A tile is 1024 consecutive bytes of one worker's bitmap row, one 256-thread
+// workgroup, thread t on bytes 4t..4t+3, so index order in a tile is (wave,
+// lane, byte). Worker w's row starts at byte w*R of the bitmap, an address of
+// no particular alignment. The tile grid is therefore laid from the 4-byte
+// aligned address at or below the row's first byte: `lead` = 0..3 bytes in
+// front of the row belong to the first word, and a row needs
+// ceil((R + 3) / 1024) tiles whatever its lead. A thread whose four bytes all
+// lie inside the row moves them as one aligned word; a thread on the row's
+// head or tail touches the bytes inside the row one by one and takes the
+// others as fresh. Nothing outside the row is read or written. Threads past
+// the end stay active through the shuffles with a count of 0.
+// ---------------------------------------------------------------------------
+
+#define STALE_TILE 1024
+
+// The thread's four bytes as a little-endian word; r0 is the first one's
+// local row, negative in the lead. `whole`: they were one aligned word.
+static __device__ __forceinline__ uint32_t stale_load(const uint8_t* row,
+                                                      int64_t r0, int64_t R,
+                                                      bool& whole) {
+  whole = r0 >= 0 && r0 + 3 < R;
+  if (whole) return *(const uint32_t*)(row + r0);
+  uint32_t word = 0x01010101u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int64_t r = r0 + k;
+    if (r >= 0 && r < R)
+      word = (word & ~(0xffu << (8 * k))) | ((uint32_t)row[r] << (8 * k));
+  }
+  return word;
+}
+
+// bit k = byte k of the word is 0
+static __device__ __forceinline__ int zero_bytes(uint32_t word) {
+  int m = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (!((word >> (8 * k)) & 0xffu)) m |= 1 << k;
+  return m;
+}
+
+// grid (tiles, workers): tile_count[worker - w0][tile] = its stale rows
+__global__ __launch_bounds__(BLOCK) void k_stale_count(
+    const uint8_t* __restrict__ bitmap, int64_t R, int w0, int tiles,
+    int* __restrict__ tile_count) {
+  __shared__ int s_wave[BLOCK / WAVE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint8_t* row = bitmap + (int64_t)(w0 + blockIdx.y) * R;
+  const int lead = (int)((uintptr_t)row & 3);
+  const int64_t r0 = (int64_t)blockIdx.x * STALE_TILE + 4 * tid - lead;
+  bool whole;
+  int c = __popc(zero_bytes(stale_load(row, r0, R, whole)));
+#pragma unroll
+  for (int m = WAVE / 2; m; m >>= 1) c += __shfl_xor(c, m, WAVE);
+  if (lane == 0) s_wave[wave] = c;
+  __syncthreads();
+  if (tid == 0)
+    tile_count[(int64_t)blockIdx.y * tiles + blockIdx.x] =
+        ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+
+#define STALE_SCAN_BLOCK 1024
+
+// One workgroup: plan[i] = the sum of tile_count[0..i), i < n = nw * tiles, in
+// (worker, tile) order, by chunks of 1024 with a running carry (a chunk sums
+// to at most 2^20, the carry is 64-bit). Behind the bases: plan[n + w] = the
+// stale rows of worker w0 + w, plan[n + nw] = all of them.
+__global__ __launch_bounds__(STALE_SCAN_BLOCK) void k_stale_scan(
+    const int* __restrict__ tile_count, int64_t* plan, int64_t n, int tiles,
+    int nw) {
+  __shared__ int s_wave[STALE_SCAN_BLOCK / WAVE];
+  __shared__ int s_chunk;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int64_t carry = 0;
+  for (int64_t c0 = 0; c0 < n; c0 += STALE_SCAN_BLOCK) {
+    const int64_t i = c0 + tid;
+    const int c = i < n ? tile_count[i] : 0;
+    const int incl = block_scan(c, s_wave, lane, wave);
+    if (i < n) plan[i] = carry + (incl - c);
+    if (tid == STALE_SCAN_BLOCK - 1) s_chunk = incl;
+    __syncthreads();
+    carry += s_chunk;
+  }
+  __syncthreads();   // the bases above are read back by other threads
+  for (int w = tid; w < nw; w += STALE_SCAN_BLOCK) {
+    int64_t end = w + 1 < nw ? plan[(int64_t)(w + 1) * tiles] : carry;
+    plan[n + w] = end - plan[(int64_t)w * tiles];
+  }
+  if (tid == 0) plan[n + nw] = carry;
+}
+
+// Same grid as k_stale_count, over the unchanged bitmap: the thread's stale
+// rows go to ids[] at the tile's base plus the thread's exclusive prefix in
+// the workgroup, ascending, and their bytes become 1. ids holds n entries; a
+// slot at or past n (the bitmap changed after the count) is not written.
+__global__ __launch_bounds__(BLOCK) void k_stale_emit(
+    uint8_t* __restrict__ bitmap, int64_t R, int w0, int tiles,
+    const int64_t* __restrict__ plan, int64_t* __restrict__ ids, int64_t n) {
+  __shared__ int s_wave[BLOCK / WAVE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  uint8_t* row = bitmap + (int64_t)(w0 + blockIdx.y) * R;
+  const int lead = (int)((uintptr_t)row & 3);
+  const int64_t r0 = (int64_t)blockIdx.x * STALE_TILE + 4 * tid - lead;
+  bool whole;
+  const uint32_t word = stale_load(row, r0, R, whole);
+  const int m = zero_bytes(word);
+  const int c = __popc(m);
+  const int incl = block_scan(c, s_wave, lane, wave);
+  if (!m) return;   // no barrier follows
+  int64_t at = plan[(int64_t)blockIdx.y * tiles + blockIdx.x] + (incl - c);
+  uint32_t fresh = word;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (!((m >> k) & 1)) continue;
+    if (at < n) ids[at] = r0 + k;
+    ++at;
+    fresh |= 1u << (8 * k);
+    if (!whole) row[r0 + k] = 1;   // a stale byte is inside the row
+  }
+  if (whole) *(uint32_t*)(row + r0) = fresh;
+}
+
+extern "C" {
+
+int64_t mv_stale_tiles(int64_t R) {
+  return (R + 3 + STALE_TILE - 1) / STALE_TILE;
+}
+
+// 1 <= R < 2^31, 1 <= nw <= 65535; tile_count holds nw * tiles int32, plan
+// nw * tiles + nw + 1 int64
+void mv_launch_stale_count(const uint8_t* bitmap, int64_t R, int w0, int nw,
+                           int* tile_count, int64_t* plan, hipStream_t s) {
+  int tiles = (int)mv_stale_tiles(R);
+  k_stale_count<<<dim3(tiles, nw), BLOCK, 0, s>>>(bitmap, R, w0, tiles,
+                                                  tile_count);
+  k_stale_scan<<<1, STALE_SCAN_BLOCK, 0, s>>>(tile_count, plan,
+                                              (int64_t)nw * tiles, tiles, nw);
+}
+
+void mv_launch_stale_emit(uint8_t* bitmap, int64_t R, int w0, int nw,
+                          const int64_t* plan, int64_t* ids, int64_t n,
+                          hipStream_t s) {
+  int tiles = (int)mv_stale_tiles(R);
+  k_stale_emit<<<dim3(tiles, nw), BLOCK, 0, s>>>(bitmap, R, w0, tiles, plan,
+                                                 ids, n);
 }
 
 }  // extern "C"

@@ -55,6 +55,19 @@ void mv_launch_topk_decode_sum(float*, const uint8_t*, int, int64_t, int,
                                hipStream_t);
 void mv_launch_row_gather(void*, int, const float*, const int64_t*, int64_t,
                           int64_t, hipStream_t);
+// destination-indexed K6: (out, shard, rows, nrows, cols), unique rows
+void mv_launch_row_gather_at(float*, const float*, const int64_t*, int64_t,
+                             int64_t, hipStream_t);
+// stale-row lists over the byte bitmap [workers, R], 1 <= R < 2^31, for nw
+// workers from w0 (1 <= nw <= 65535). tiles(R) is the tiles per worker.
+// count (bitmap, R, w0, nw, tile_count [nw*tiles], plan): plan [nw*tiles + nw
+// + 1] gets the tile bases, then each worker's total, then the grand total.
+// emit (bitmap, R, w0, nw, plan, ids [n], n) over the unchanged bitmap.
+int64_t mv_stale_tiles(int64_t);
+void mv_launch_stale_count(const uint8_t*, int64_t, int, int, int*, int64_t*,
+                           hipStream_t);
+void mv_launch_stale_emit(uint8_t*, int64_t, int, int, const int64_t*,
+                          int64_t*, int64_t, hipStream_t);
 void mv_launch_row_scatter_add(float*, const void*, int, const int64_t*, float,
                                int64_t, int64_t, int, hipStream_t);
 void mv_launch_row_scatter_adagrad(float*, float*, const void*, int,

@@ -11,8 +11,9 @@ a local cache of the whole table and only stale rows travel.
 
 MI355X mapping: the bitmap lives with the owning shard as a bool tensor in
 HBM; ``get_into(cache)`` is a collective where each owner builds each
-requester's stale row list (a masked select), serves those rows (K6
-gather) and marks them fresh; the rows travel in one all-to-all. Keyed
+requester's stale row list and marks it fresh (``_take_stale``: one stream
+compaction over the bitmap for all requesters, k_stale_* in HIP) and serves
+those rows (K6 gather); the rows travel in one all-to-all. Keyed
 adds travel through the base class and invalidate per source rank."""
 
 from __future__ import annotations
@@ -50,6 +51,10 @@ class SparseMatrixTable(MatrixTable):
         # up_to_date[w, r] == True -> worker w has the current row r
         self.up_to_date = torch.zeros(nw, self.local_rows, dtype=torch.bool,
                                       device=self.device)
+        # stale lists from the HIP compaction kernels (the kernels index a
+        # shard's rows with 32 bits; tools/probe_stale_get.py turns this off
+        # to time the torch path)
+        self._hip_stale = self.up_to_date.is_cuda and self.local_rows < 2 ** 31
         self._ready.set()
 
     # ---- invalidation hooks ----
@@ -73,19 +78,46 @@ class SparseMatrixTable(MatrixTable):
         with self._shard_lock:
             self.up_to_date.zero_()   # whole-shard add: everyone stale
 
+    def _take_stale(self, w0: int, w1: int):
+        """The rows of MY shard stale for the workers ``[w0, w1)``:
+        ``(counts, local_ids)`` with one count per worker and the local row
+        ids ascending inside a worker, the workers in order. The listed rows
+        are marked fresh. On a GPU bitmap this is k_stale_count /
+        k_stale_scan / k_stale_emit, three launches and one synchronisation
+        for all the workers; the caller holds ``_shard_lock`` wherever another
+        thread can reach the bitmap, since it must not change between the
+        two calls."""
+        if self._hip_stale:
+            from .. import ops
+            hip = ops.module(required=True)
+            plan, totals = hip.stale_count(self.up_to_date, w0, w1)
+            counts = totals.tolist()
+            return counts, hip.stale_emit(self.up_to_date, plan, w0, w1,
+                                          sum(counts))
+        stale_lists = [(~self.up_to_date[w]).nonzero().reshape(-1)
+                       for w in range(w0, w1)]
+        counts = [int(s.numel()) for s in stale_lists]
+        for w, stale in zip(range(w0, w1), stale_lists):
+            if stale.numel():
+                self.up_to_date[w, stale] = True
+        if not sum(counts):
+            return counts, torch.empty(0, dtype=torch.int64,
+                                       device=self.device)
+        return counts, torch.cat(stale_lists)
+
+    def _served_rows(self, local_ids: torch.Tensor) -> torch.Tensor:
+        if local_ids.numel():
+            return self._gather_local(local_ids)
+        return torch.empty(0, self.num_col, dtype=self.dtype,
+                           device=self.device)
+
     def _server_stale_for(self, worker: int):
         """Rows of MY shard stale for ``worker``: gather them, mark them
         fresh, return (global_ids, values). UpdateGetState semantics
         (sparse_matrix_table.cpp:226-258) served on arrival."""
         with self._shard_lock:
-            stale = (~self.up_to_date[worker]).nonzero().reshape(-1)
-            if stale.numel():
-                served = self._gather_local(stale)
-                self.up_to_date[worker, stale] = True
-            else:
-                served = torch.empty(0, self.num_col, dtype=self.dtype,
-                                     device=self.device)
-            return stale + self.row_offset, served
+            _, stale = self._take_stale(worker, worker + 1)
+            return stale + self.row_offset, self._served_rows(stale)
 
     def _server_add_rows(self, local_ids, vals2d, option) -> None:
         super()._server_add_rows(local_ids, vals2d, option)
@@ -168,30 +200,21 @@ class SparseMatrixTable(MatrixTable):
             return h
         nw = self.zoo.num_workers
         with monitor("worker.sparse_prefetch"):
-            stale_lists = [(~self.up_to_date[w]).nonzero().reshape(-1)
-                           for w in range(nw)]
-            send_rows = [int(s.numel()) for s in stale_lists]
+            with self._shard_lock:
+                send_rows, stale = self._take_stale(0, nw)
             recv_rows = exchange_sizes(send_rows)
-            all_ids = (torch.cat(stale_lists) + self.row_offset
-                       if sum(send_rows) else
-                       torch.empty(0, dtype=torch.int64, device=self.device))
+            all_ids = stale + self.row_offset
             got_ids = torch.empty(sum(recv_rows), dtype=torch.int64,
                                   device=self.device)
             w1 = dist.all_to_all_single(got_ids, all_ids, recv_rows,
                                         send_rows, async_op=True)
-            served = (self._gather_local(torch.cat(stale_lists))
-                      if sum(send_rows) else
-                      torch.empty(0, self.num_col, dtype=self.dtype,
-                                  device=self.device))
+            served = self._served_rows(stale)
             got_vals = torch.empty(sum(recv_rows) * self.num_col,
                                    dtype=self.dtype, device=self.device)
             w2 = dist.all_to_all_single(
                 got_vals, served.reshape(-1),
                 [r * self.num_col for r in recv_rows],
                 [s * self.num_col for s in send_rows], async_op=True)
-            for w in range(nw):
-                if send_rows[w]:
-                    self.up_to_date[w, stale_lists[w]] = True
 
         def finish() -> None:
             w1.wait()
@@ -219,36 +242,35 @@ class SparseMatrixTable(MatrixTable):
         nw = self.zoo.num_workers
         with monitor("worker.sparse_get"):
             if self.zoo.size == 1:
-                stale = (~self.up_to_date[0]).nonzero().reshape(-1)
-                if stale.numel():
+                with self._shard_lock:
+                    (n,), stale = self._take_stale(0, 1)
+                if n and (cache.is_cuda and cache.is_contiguous()
+                          and cache.dtype == self.dtype == torch.float32):
+                    from .. import ops
+                    ops.module(required=True).row_gather_at(
+                        cache, self.shard, stale)
+                elif n:
                     cache[stale] = self._gather_local(stale)
-                    self.up_to_date[0, stale] = True
-                return int(stale.numel())
-            # 1) each owner builds per-requester stale lists
-            stale_lists = [(~self.up_to_date[w]).nonzero().reshape(-1)
-                           for w in range(nw)]
-            send_rows = [int(s.numel()) for s in stale_lists]
+                return n
+            # 1) each owner builds per-requester stale lists and marks them
+            # fresh (no other table op runs before this Get returns)
+            with self._shard_lock:
+                send_rows, stale = self._take_stale(0, nw)
             # 2) counts ride the control lane; then ids+values
             from ..comm import exchange_sizes
             recv_rows = exchange_sizes(send_rows)
-            all_ids = torch.cat(stale_lists) + self.row_offset
+            all_ids = stale + self.row_offset
             got_ids = torch.empty(sum(recv_rows), dtype=torch.int64,
                                   device=self.device)
             dist.all_to_all_single(got_ids, all_ids, recv_rows, send_rows)
-            served = (self._gather_local(torch.cat(stale_lists))
-                      if all_ids.numel() else
-                      torch.empty(0, self.num_col, dtype=self.dtype,
-                                  device=self.device))
+            served = self._served_rows(stale)
             if self.use_sparse_filter:
                 got_vals = self._filtered_value_exchange(
                     served, send_rows, recv_rows)
             else:
                 got_vals = all_to_all_values(served.view(-1), send_rows,
                                              recv_rows, self.num_col)
-            # 3) write into cache; mark fresh on the server side
+            # 3) write into cache
             if got_ids.numel():
                 cache[got_ids] = got_vals.view(-1, self.num_col)
-            for w in range(nw):
-                if send_rows[w]:
-                    self.up_to_date[w, stale_lists[w]] = True
             return int(got_ids.numel())
