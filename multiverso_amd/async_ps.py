@@ -43,6 +43,7 @@ from typing import List, Optional
 import torch
 import torch.distributed as dist
 
+from .comm import csr_of
 from .dashboard import monitor
 from .log import CHECK, log
 from .updaters import AddOption
@@ -62,6 +63,9 @@ OP_NEAREST = 10     # nearest_rows: payload = Q fp32 queries of num_col;
                     # reply = one blob, Q*k int64 global ids then Q*k fp32
                     # scores. Header: n_keys = Q, n_vals = k, has_opt = 1
                     # for cosine and 0 for dot (the request has no option)
+OP_POOL_ROWS = 11   # pool_rows: one blob [ids: n_keys i64][part lengths:
+                    # n_vals i64][weights: n_keys fp32 if has_opt]; reply =
+                    # n_vals pooled rows of num_col in the wire dtype
 
 _HDR = 6  # int64 fields: [op, table_id, n_keys, n_vals, want_ack, has_opt]
 
@@ -342,6 +346,53 @@ class AsyncEngine:
                     torch.empty(0, 0, dtype=torch.int64, device=table.device))
         return torch.cat(scores, 1), torch.cat(ids, 1)
 
+    def pool(self, table, ids_cpu: torch.Tensor,
+             weights: Optional[torch.Tensor], plan):
+        """pool_rows: every server that owns some of the ids sums its part
+        of each bag on arrival. Returns per server ``(bag index of each part,
+        its pooled rows)`` for the caller to merge in server order. The reply
+        holds one row per part, so its recv is posted at send time; the local
+        shard is served without the transport, and a server that owns none of
+        the ids gets no message."""
+        zoo = self.zoo
+        unit = table.num_col
+        sorted_ids = ids_cpu[plan.order]
+        sorted_w = (None if weights is None
+                    else weights[plan.order.to(weights.device)])
+        works: List = []
+        refs: List = []
+        parts = []
+        id0 = part0 = 0
+        for s, (cnt, np_) in enumerate(zip(plan.n_ids, plan.n_parts)):
+            if cnt == 0:
+                continue
+            dst = zoo.server_ranks[s]
+            keys = sorted_ids[id0:id0 + cnt]
+            lens = plan.part_len[part0:part0 + np_]
+            bags = plan.part_bag[part0:part0 + np_]
+            w = None if sorted_w is None else sorted_w[id0:id0 + cnt]
+            id0 += cnt
+            part0 += np_
+            if dst == zoo.rank:
+                parts.append((bags, table._server_pool(
+                    (keys - table.row_offset).to(table.device),
+                    csr_of(lens).to(table.device), w)))
+                continue
+            hdr = [OP_POOL_ROWS, table.table_id, cnt, np_, 0,
+                   0 if w is None else 1]
+            ps = [keys.contiguous(), lens.contiguous()]
+            if w is not None:
+                ps.append(w.cpu().contiguous())
+            wk, r = self._send_request(dst, hdr, ps)
+            works += wk
+            refs += r
+            buf = torch.empty(np_, unit, dtype=table.wire)
+            works.append(dist.irecv(buf, dst, group=self.rep))
+            parts.append((bags, buf))
+        for wk in works:
+            wk.wait()
+        return parts
+
     def kv_add(self, table, keys: torch.Tensor, vals: torch.Tensor):
         """KVTable add: key % num_servers sharding (kv_table.h:49)."""
         zoo = self.zoo
@@ -540,6 +591,21 @@ class AsyncEngine:
                 [ids.cpu().contiguous().view(torch.uint8).view(-1),
                  scores.cpu().contiguous().view(torch.uint8).view(-1)]),
                 src, group=self.rep)
+            return
+        if op == OP_POOL_ROWS:
+            # n_keys = ids (> 0), n_vals = parts, has_opt = weighted
+            blob = torch.empty(n_keys * (12 if has_opt else 8) + n_vals * 8,
+                               dtype=torch.uint8)
+            dist.recv(blob, src, group=self.req)
+            keys = blob[:n_keys * 8].view(torch.int64)
+            lens = blob[n_keys * 8:(n_keys + n_vals) * 8].view(torch.int64)
+            w = (blob[(n_keys + n_vals) * 8:].view(torch.float32)
+                 .to(table.device) if has_opt else None)
+            with monitor("server.process_get"):
+                got = table._server_pool(
+                    (keys - table.row_offset).to(table.device),
+                    csr_of(lens).to(table.device), w)
+            dist.send(got.cpu().contiguous(), src, group=self.rep)
             return
         # One blob recv mirrors the worker's one blob send (layout in
         # _send_request: [opt][keys][vals], 8-byte aligned sections)

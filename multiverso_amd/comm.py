@@ -13,6 +13,9 @@ MI355X-native mapping (BASELINE.json north star):
 - row-keyed Get/Add = all-to-all exchange (keys, then values) — irregular
   p2p traffic is batched per destination, which matches xGMI's 7
   point-to-point links far better than a ring of small messages
+- pooled row Get (``pool_rows``) = the same keyed all-to-all, but a bag's
+  ids travel with their part lengths (``plan_bags``, ``all_to_all_bags``) and
+  one pooled row per bag and owner comes back instead of one row per id
 - aggregate (MV_Aggregate / -ma mode) = one all-reduce
 - bf16 wire format (tables built with ``wire_dtype=torch.bfloat16``): the
   same collectives carry bfloat16 payloads for an fp32 shard. Nothing here is
@@ -332,6 +335,73 @@ def all_to_all_rows(row_ids: torch.Tensor, values: Optional[torch.Tensor],
                                [c * unit for c in recv_sizes],
                                [c * unit for c in send_sizes])
     return in_ids, in_vals, recv_sizes, order, send_sizes
+
+
+class BagPlan:
+    """A pooled Get's ids split by owner (``plan_bags``). ``order`` groups the
+    ids by owner with the stable sort of ``all_to_all_rows``, so inside an
+    owner they stay grouped by bag, in caller order. A part is the run of one
+    bag's ids on one owner: ``part_len`` / ``part_bag`` hold every part's
+    length and bag index, owner-major; ``n_ids[s]`` / ``n_parts[s]`` are the
+    ids and the parts (bags touched) of owner ``s``. All on the host."""
+
+    def __init__(self, order, n_ids, n_parts, part_len, part_bag) -> None:
+        self.order = order
+        self.n_ids: List[int] = n_ids
+        self.n_parts: List[int] = n_parts
+        self.part_len = part_len
+        self.part_bag = part_bag
+
+
+def plan_bags(ids_cpu: torch.Tensor, offsets_cpu: torch.Tensor,
+              spec: ShardSpec) -> BagPlan:
+    """Host planning of ``pool_rows``: CPU int64 ids ``[nnz]`` and CSR
+    offsets ``[B+1]``, both already validated."""
+    n_bags = offsets_cpu.numel() - 1
+    bag_of = torch.repeat_interleave(torch.arange(n_bags), offsets_cpu.diff())
+    base = max(spec.total // spec.n, 1)
+    owners = torch.div(ids_cpu, base,
+                       rounding_mode="floor").clamp_(max=spec.n - 1)
+    order = torch.argsort(owners, stable=True)
+    # (owner, bag) is non-decreasing along the sorted list: equal neighbours
+    # are one part
+    key, part_len = torch.unique_consecutive(
+        owners[order] * max(n_bags, 1) + bag_of[order], return_counts=True)
+    part_owner = torch.div(key, max(n_bags, 1), rounding_mode="floor")
+    return BagPlan(order,
+                   torch.bincount(owners, minlength=spec.n).tolist(),
+                   torch.bincount(part_owner, minlength=spec.n).tolist(),
+                   part_len, key - part_owner * max(n_bags, 1))
+
+
+def csr_of(lengths: torch.Tensor) -> torch.Tensor:
+    """CSR offsets ``[len + 1]`` of a list of bag lengths, same device."""
+    out = lengths.new_zeros(lengths.numel() + 1)
+    out[1:] = lengths.cumsum(0)
+    return out
+
+
+def all_to_all_bags(ids_cpu: torch.Tensor, weights: Optional[torch.Tensor],
+                    plan: BagPlan, device: torch.device
+                    ) -> Tuple[torch.Tensor, torch.Tensor,
+                               Optional[torch.Tensor], List[int]]:
+    """Request half of a pooled Get on the sync plane: every owner receives
+    the ids, the part lengths and (``weights`` given, fp32 on ``device``) the
+    weights of every requester's parts on its shard. Returns
+    ``(in_ids, in_offsets, in_weights, recv_parts)``: all requesters' parts as
+    one CSR, requester-major, and the parts each requester sent, which is the
+    reply's split. Both counts per destination ride the control lane in one
+    message; ``weights is None`` must agree across ranks."""
+    recv_ids, recv_parts = exchange_size_rows([plan.n_ids, plan.n_parts])
+    in_ids = all_to_all_values(ids_cpu[plan.order].to(device), plan.n_ids,
+                               recv_ids, 1)
+    in_lens = all_to_all_values(plan.part_len.to(device), plan.n_parts,
+                                recv_parts, 1)
+    in_w = None
+    if weights is not None:
+        in_w = all_to_all_values(weights[plan.order.to(device)], plan.n_ids,
+                                 recv_ids, 1)
+    return in_ids, csr_of(in_lens), in_w, recv_parts
 
 
 def all_to_all_values(values: torch.Tensor, send_sizes: List[int],

@@ -366,6 +366,45 @@ void row_gather_at(torch::Tensor out, torch::Tensor shard,
                           rows.numel(), shard.size(1), cur_stream());
 }
 
+// Pooled rows (k_row_pool): out[b] = sum over offsets[b] <= i < offsets[b+1]
+// of shard[rows[i]] (times weights[i]), fp32 or, with dtype, bf16. The row
+// range and what offsets holds (0 first, nnz last, non-decreasing) lie in
+// device memory and are not checked here (that would take a sync): the table
+// checks them on the host copy it plans from.
+torch::Tensor row_pool(torch::Tensor shard, torch::Tensor rows,
+                       torch::Tensor offsets,
+                       c10::optional<torch::Tensor> weights,
+                       c10::optional<torch::ScalarType> dtype) {
+  check_f32(shard, "shard");
+  TORCH_CHECK(shard.dim() == 2 && shard.size(1) >= 1,
+              "shard must be 2-D with at least one column");
+  check_dev(rows, "rows", torch::kInt64);
+  check_dev(offsets, "offsets", torch::kInt64);
+  TORCH_CHECK(offsets.numel() >= 1, "offsets needs at least one entry");
+  int64_t nnz = rows.numel(), B = offsets.numel() - 1;
+  TORCH_CHECK(nnz <= INT32_MAX && B <= INT32_MAX,
+              "row_pool takes fewer than 2^31 ids and bags");
+  TORCH_CHECK(nnz == 0 || shard.size(0) >= 1, "ids into an empty shard");
+  const float* wts = nullptr;
+  if (weights.has_value()) {
+    check_f32(*weights, "weights");
+    TORCH_CHECK(weights->numel() == nnz, "weights size mismatch");
+    wts = f32(*weights);
+  }
+  auto wire = dtype.value_or(torch::kFloat32);
+  TORCH_CHECK(wire == torch::kFloat32 || wire == torch::kBFloat16,
+              "dtype must be fp32 or bf16");
+  auto opt = shard.options().dtype(wire);
+  // no ids: every bag is empty, zeros without a launch
+  if (!B || !nnz) return torch::zeros({B, shard.size(1)}, opt);
+  auto out = torch::empty({B, shard.size(1)}, opt);
+  mv_launch_row_pool(out.data_ptr(), wire == torch::kBFloat16 ? kWireOut : 0,
+                     f32(shard), rows.data_ptr<int64_t>(),
+                     offsets.data_ptr<int64_t>(), wts, B, shard.size(1),
+                     cur_stream());
+  return out;
+}
+
 // Stale-row lists of SparseMatrixTable: bitmap [workers, R] of bytes, 0 =
 // stale. Returns the row count R; the worker range is [w0, w1).
 int64_t check_bitmap(const torch::Tensor& bitmap, int64_t w0, int64_t w1) {
@@ -1027,6 +1066,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("row_gather_at", &row_gather_at,
         "K6 in place: out[rows[i]] = shard[rows[i]], unique rows",
         py::arg("out"), py::arg("shard"), py::arg("rows"));
+  m.def("row_pool", &row_pool,
+        "pooled rows: out[b] = sum of shard[rows[i]] (times weights[i]) over "
+        "offsets[b] <= i < offsets[b+1], in list order; "
+        "dtype=torch.bfloat16 narrows",
+        py::arg("shard"), py::arg("rows"), py::arg("offsets"),
+        py::arg("weights") = py::none(), py::arg("dtype") = py::none());
   m.def("stale_count", &stale_count,
         "stale rows per worker in [w0, w1) of a byte bitmap [workers, rows] "
         "(0 = stale): (plan for stale_emit, CPU int64 totals)",

@@ -2719,6 +2719,205 @@ extern "C" void mv_launch_lr_dense_post_wide(float* logits,
 }
 
 // ---------------------------------------------------------------------------
+// Pooled rows (MatrixTable.pool_rows, the embedding-bag read): out[b] is the
+// (weighted) sum of the shard rows rows[offsets[b] .. offsets[b+1]), so that a
+// bag of L ids costs the caller one row instead of L.
+//
+// k_row_pool<G, VPL, V, O, WEIGHTED>: a bag is served by a group of G lanes
+// (a power of two, 4..64; 64 / G bags share a wave), each lane keeping VPL
+// column vectors V (v4f when cols % 4 == 0, else float) of the bag's sum in
+// registers: lane j owns vectors j, j + G, ... of its column panel. G is the
+// smallest group that covers the row, so a 64-column row takes 16 lanes of
+// v4f and four bags a wave; a row wider than 64 * POOL_VPL_MAX vectors is cut
+// into panels over gridDim.y. Bags go to groups by a grid-stride loop.
+//
+// A group stages G consecutive ids (and weights) of its bag with one
+// coalesced load, lane j holding item j, and then walks them: each item is
+// broadcast inside the group (__shfl of width G; v_readlane when G = 64, so
+// the row base is scalar), the row loads of pool_u(VPL) consecutive items are
+// all issued before the first add. Row addresses are 64-bit.
+//
+// Ordering contract: inside a bag the rows are added in list order, starting
+// from +0.0, acc = acc + x or acc = fmaf(w, x, acc). One lane sums one column
+// serially, so the result is repeatable bit for bit and does not depend on
+// the grid or on the bags that share the wave. No atomics, LDS or scratch.
+//
+// The bags of a wave are ragged: every loop runs to the wave's longest bag
+// and is scalar. A group past its own end keeps loading from a valid address
+// (the item index is clamped to its bag's last item, or to item 0 for an
+// empty bag; the columns are clamped like wide_cols) and drops the value
+// with a select: an inf in such a row never reaches a bag that does not list
+// it. The shard is read with plain loads (rows repeat across bags, the
+// caches help); the sums are stored once, through st: non-temporal v4f, or
+// packed bf16.
+//
+// Known limit, as in k_row_update: one group walks its bag serially, so a
+// bag of tens of thousands of ids stretches the launch to that bag's length.
+// ---------------------------------------------------------------------------
+
+// 4 blocks of 4 waves on each of the 256 CUs
+#define POOL_GRID 1024
+#define POOL_VPL_MAX 4
+// items whose row loads a group keeps in flight: up to 8 v4f a lane, the
+// budget of wide_nf
+constexpr int pool_u(int vpl) { return vpl <= 2 ? 4 : 2; }
+
+// value of lane `src` of this lane's group; src is wave-uniform
+template <int G, class T>
+static __device__ __forceinline__ T pool_bcast(T v, int src) {
+  if constexpr (G == 64) return lane_bcast(v, src);
+  else return __shfl(v, src, G);
+}
+
+static __device__ __forceinline__ float pool_step(float acc, float x, float w,
+                                                  bool weighted) {
+  return weighted ? __builtin_fmaf(w, x, acc) : acc + x;
+}
+static __device__ __forceinline__ v4f pool_step(v4f acc, v4f x, float w,
+                                                bool weighted) {
+  v4f r;
+  r.x = pool_step(acc.x, x.x, w, weighted);
+  r.y = pool_step(acc.y, x.y, w, weighted);
+  r.z = pool_step(acc.z, x.z, w, weighted);
+  r.w = pool_step(acc.w, x.w, w, weighted);
+  return r;
+}
+
+// N staged items, t .. t+N-1 of the round held in (rid, w) across the group's
+// lanes; item t+u belongs to the bag while t + u < left. All N * VPL loads
+// are issued before the first add.
+template <int G, int VPL, int N, bool WEIGHTED, class V>
+static __device__ __forceinline__ void pool_items(
+    V (&acc)[VPL], const V* __restrict__ shard, int vcols,
+    const int (&col)[VPL], int64_t rid, float w, int t, int left) {
+  V x[N][VPL];
+  float wv[N];
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    const V* row = shard + pool_bcast<G>(rid, t + u) * (int64_t)vcols;
+    wv[u] = WEIGHTED ? pool_bcast<G>(w, t + u) : 0.f;
+#pragma unroll
+    for (int r = 0; r < VPL; ++r) x[u][r] = row[col[r]];
+  }
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    bool live = t + u < left;
+#pragma unroll
+    for (int r = 0; r < VPL; ++r)
+      acc[r] = live ? pool_step(acc[r], x[u][r], wv[u], WEIGHTED) : acc[r];
+  }
+}
+
+// B >= 1 bags over nnz >= 1 ids; vcols counts V's per row
+template <int G, int VPL, class V, class O, bool WEIGHTED>
+__global__ __launch_bounds__(BLOCK) void k_row_pool(
+    O* __restrict__ out, const V* __restrict__ shard,
+    const int64_t* __restrict__ rows, const int64_t* __restrict__ offsets,
+    const float* __restrict__ wts, int B, int vcols) {
+  constexpr int U = pool_u(VPL), GPW = WAVE / G;
+  const int lane = threadIdx.x & 63, j = lane & (G - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(
+      (int)((blockIdx.x * BLOCK + threadIdx.x) >> 6));
+  const int nwaves = gridDim.x * (BLOCK / WAVE);
+  int col[VPL];
+  bool own[VPL];
+#pragma unroll
+  for (int r = 0; r < VPL; ++r) {
+    int c = blockIdx.y * (G * VPL) + j + G * r;
+    own[r] = c < vcols;
+    col[r] = own[r] ? c : vcols - 1;
+  }
+  for (int b0 = wave * GPW; b0 < B; b0 += nwaves * GPW) {
+    const int b = b0 + lane / G;
+    const bool bag = b < B;
+    const int bc = bag ? b : B - 1;
+    const int64_t begin = offsets[bc];
+    const int len = bag ? (int)(offsets[bc + 1] - begin) : 0;
+    const int64_t last = len > 0 ? begin + len - 1 : 0;
+    int longest = len;
+#pragma unroll
+    for (int sh = G; sh < WAVE; sh <<= 1)
+      longest = max(longest, __shfl_xor(longest, sh, WAVE));
+    longest = __builtin_amdgcn_readfirstlane(longest);
+    V acc[VPL];
+#pragma unroll
+    for (int r = 0; r < VPL; ++r) acc[r] = V{};
+    for (int base = 0; base < longest; base += G) {
+      int64_t at = begin + base + j;
+      at = at < last ? at : last;
+      const int64_t rid = rows[at];
+      const float w = WEIGHTED ? wts[at] : 0.f;
+      const int cnt = min(G, longest - base), left = len - base;
+      int t = 0;
+      for (; t + U <= cnt; t += U)
+        pool_items<G, VPL, U, WEIGHTED>(acc, shard, vcols, col, rid, w, t,
+                                        left);
+      for (; t < cnt; ++t)
+        pool_items<G, VPL, 1, WEIGHTED>(acc, shard, vcols, col, rid, w, t,
+                                        left);
+    }
+#pragma unroll
+    for (int r = 0; r < VPL; ++r)
+      if (bag && own[r]) st(out, (int64_t)b * vcols + col[r], acc[r]);
+  }
+}
+
+// f(kint<G>(), kint<VPL>()) for a row of vcols vectors: the smallest group
+// that covers it, then the VPL buckets 1, 2, 4 of a whole wave
+template <class F>
+static void with_pool_shape(int64_t vcols, F f) {
+  if (vcols <= 4) f(kint<4>(), kint<1>());
+  else if (vcols <= 8) f(kint<8>(), kint<1>());
+  else if (vcols <= 16) f(kint<16>(), kint<1>());
+  else if (vcols <= 32) f(kint<32>(), kint<1>());
+  else if (vcols <= 64) f(kint<64>(), kint<1>());
+  else if (vcols <= 128) f(kint<64>(), kint<2>());
+  else f(kint<64>(), kint<POOL_VPL_MAX>());
+}
+
+// The v4f form needs cols % 4 == 0 and out's vector store alignment (16 bytes
+// fp32, 8 bytes bf16, as launch_row_gather checks); everything else takes the
+// scalar form of the same source. B and nnz are below 2^31 (the binding
+// refuses more) and not 0.
+template <class O>
+static void launch_row_pool(O* out, const float* shard, const int64_t* rows,
+                            const int64_t* offsets, const float* wts,
+                            int64_t B, int64_t cols, hipStream_t s) {
+  constexpr bool narrow_out = std::is_same<O, bf16>::value;
+  bool vec = cols % 4 == 0 && aligned16(shard) &&
+             (narrow_out ? ((uintptr_t)out & 7) == 0 : aligned16(out));
+  int64_t vcols = vec ? cols / 4 : cols;
+  with_pool_shape(vcols, [&](auto g, auto v) {
+    constexpr int G = decltype(g)::value, VPL = decltype(v)::value;
+    int64_t per_block = BLOCK / G, panel = G * VPL;
+    dim3 grid((unsigned)grid_for_cap((B + per_block - 1) / per_block * BLOCK,
+                                     POOL_GRID),
+              (unsigned)((vcols + panel - 1) / panel));
+    auto go = [&](auto* sh) {
+      using V = ELEM_OF(sh);
+      if (wts)
+        k_row_pool<G, VPL, V, O, true><<<grid, BLOCK, 0, s>>>(
+            out, sh, rows, offsets, wts, (int)B, (int)vcols);
+      else
+        k_row_pool<G, VPL, V, O, false><<<grid, BLOCK, 0, s>>>(
+            out, sh, rows, offsets, wts, (int)B, (int)vcols);
+    };
+    if (vec) go((const v4f*)shard);
+    else go(shard);
+  });
+}
+
+extern "C" void mv_launch_row_pool(void* out, int wire, const float* shard,
+                                   const int64_t* rows, const int64_t* offsets,
+                                   const float* wts, int64_t B, int64_t cols,
+                                   hipStream_t s) {
+  if (!B || !cols) return;
+  with_wire(wire, nullptr, out, [&](auto*, auto* o) {
+    launch_row_pool(o, shard, rows, offsets, wts, B, cols, s);
+  });
+}
+
+// ---------------------------------------------------------------------------
 // Nearest rows (MatrixTable.nearest_rows): the k best rows of the shard for
 // each of Q queries, in two plain launches with no atomics and no
 // cross-workgroup communication.

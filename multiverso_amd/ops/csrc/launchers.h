@@ -58,6 +58,13 @@ void mv_launch_row_gather(void*, int, const float*, const int64_t*, int64_t,
 // destination-indexed K6: (out, shard, rows, nrows, cols), unique rows
 void mv_launch_row_gather_at(float*, const float*, const int64_t*, int64_t,
                              int64_t, hipStream_t);
+// pooled rows: (out [B, cols], wire, shard, rows [nnz], offsets [B+1],
+// weights [nnz] or null, B, cols); out[b] = sum of shard[rows[i]] (times
+// weights[i]) over offsets[b] <= i < offsets[b+1], in list order. B and nnz
+// are below 2^31 and nnz is not 0; B == 0 launches nothing.
+void mv_launch_row_pool(void*, int, const float*, const int64_t*,
+                        const int64_t*, const float*, int64_t, int64_t,
+                        hipStream_t);
 // stale-row lists over the byte bitmap [workers, R], 1 <= R < 2^31, for nw
 // workers from w0 (1 <= nw <= 65535). tiles(R) is the tiles per worker.
 // count (bitmap, R, w0, nw, tile_count [nw*tiles], plan): plan [nw*tiles + nw

@@ -44,6 +44,12 @@ MI355X mapping:
   and only ``k`` (score, id) pairs per query per shard cross the wire; ``merge_topk`` holds the one ordering
   rule. float32 tables, ``k <= 64``, dot or cosine.
 
+- ``pool_rows`` = the embedding-bag read (sum or mean of the rows of each
+  bag, optionally weighted) reduced where the rows live: each owner sums its
+  part of every bag in caller order (k_row_pool) and one row per bag it
+  touches crosses the wire instead of one per id; the caller adds the owners'
+  partials in server order.
+
 Sparse/stale-aware Get (SparseMatrixTable's per-(worker,row) freshness
 bitmap) is implemented in sparse_matrix.py on top of this class; it takes no
 ``wire_dtype``.
@@ -55,8 +61,8 @@ from typing import Optional, Tuple
 
 import torch
 
-from ..comm import (Handle, ShardSpec, all_to_all_rows, all_to_all_values,
-                    exchange_sizes)
+from ..comm import (Handle, ShardSpec, all_to_all_bags, all_to_all_rows,
+                    all_to_all_values, exchange_sizes, plan_bags)
 from ..dashboard import monitor
 from ..log import CHECK
 from ..updaters import AddOption
@@ -338,6 +344,140 @@ class MatrixTable(DenseTable):
                                self.row_offset + self.local_rows,
                                device=s.device).expand(s.shape[0], -1)
             return merge_topk(s, ids, k)
+
+    # ---- pooled rows: the embedding-bag read, reduced where the rows live ----
+    def pool_rows(self, row_ids, offsets, weights=None, mode: str = "sum"
+                  ) -> torch.Tensor:
+        """The (weighted) sum or mean of the rows of each bag: float32
+        ``[B, num_col]`` on the table's device.
+
+        ``row_ids`` is int64 ``[nnz]``, global row ids in any order,
+        duplicates allowed inside a bag and across bags. ``offsets`` is int64
+        ``[B+1]`` CSR (``offsets[0] == 0``, ``offsets[B] == nnz``,
+        non-decreasing): bag b is ``row_ids[offsets[b]:offsets[b+1]]``. An
+        empty bag gives a row of ``+0.0``; ``B == 0`` returns ``[0, num_col]``.
+        ``weights`` is an optional float ``[nnz]``, one per id, which travels
+        as fp32. ``mode="mean"`` divides each sum once by the bag's full
+        length (weights do not enter the divisor; empty bags stay zero).
+        Planning runs on the host like ``get_rows``: CPU ids and offsets are
+        sync-free, device ids cost one D2H copy.
+
+        Every owner sums its part of each bag (k_row_pool on a float32 GPU
+        shard, torch ops otherwise) and only one row per bag it touches
+        crosses the wire, against one per id for ``get_rows``. Ordering, at
+        every level: inside an owner a bag's rows are added in caller order
+        from ``+0.0`` (``acc + x``, weighted ``fma(w, x, acc)``); the owners'
+        partials are added in server order. With L ids in a bag, n owners
+        touched and ``S = sum|w_i||x_i|``, every element is within
+        ``(L + n + 1) * 2^-24 * S`` of the exact value, and exact on
+        integer-valued data. On a bf16-wire table each owner's partial is
+        rounded to bf16 once, on a single rank too, and the partials are
+        widened and summed in fp32. inf and NaN rows poison the bags that
+        list them and no other.
+
+        A Get: a deferred Add is flushed first, updater state and the sparse
+        table's freshness bitmap are not touched. On the sync plane it is a
+        collective like ``get_rows``: every rank calls it with its own bags
+        (``B == 0`` included) and the same ``weights is None`` (not checked).
+        Float tables only. One lane group walks a bag serially, so a bag of
+        tens of thousands of ids is slow (the limit of k_row_update)."""
+        self.flush()   # a deferred whole-table Add must land first
+        CHECK(self.dtype.is_floating_point,
+              f"pool_rows needs a float table, not {self.dtype}")
+        CHECK(mode in ("sum", "mean"),
+              f"pool_rows mode {mode!r} is not known ('sum' or 'mean')")
+        ids = torch.as_tensor(row_ids, dtype=torch.int64).reshape(-1)
+        if ids.is_cuda:
+            from ..dashboard import Dashboard
+            Dashboard.get("comm.keyed_d2h").count += 1
+        ids = ids.cpu()
+        offs = torch.as_tensor(offsets, dtype=torch.int64).cpu()
+        nnz = ids.numel()
+        CHECK(offs.dim() == 1 and offs.numel() >= 1 and int(offs[0]) == 0
+              and int(offs[-1]) == nnz and bool((offs.diff() >= 0).all()),
+              f"pool_rows offsets must be CSR [B+1]: 0 first, nnz={nnz} "
+              f"last, non-decreasing")
+        lo, hi = ids.aminmax() if nnz else (0, 0)
+        CHECK(int(lo) >= 0 and int(hi) < self.num_row,
+              f"pool_rows row_ids must lie in [0, {self.num_row})")
+        w = None
+        if weights is not None:
+            w = torch.as_tensor(weights)
+            CHECK(w.is_floating_point() and w.numel() == nnz,
+                  f"pool_rows weights must be float [{nnz}], got "
+                  f"{w.dtype} {tuple(w.shape)}")
+            w = w.reshape(-1).to(self.device, torch.float32)
+        n_bags = offs.numel() - 1
+        eng = self.engine
+        with monitor("worker.pool_rows"):
+            if eng is not None:
+                CHECK(self.zoo.is_worker,
+                      "pool_rows: ps_role=server ranks issue no Gets")
+                out = self._pool_merge(
+                    n_bags, eng.pool(self, ids, w, plan_bags(ids, offs,
+                                                             self.spec)))
+            elif self.zoo.size > 1:
+                out = self._pool_merge(n_bags,
+                                       self._pool_exchange(ids, offs, w))
+            else:
+                # one owner holds every row: no permutation and no merge
+                out = self._server_pool(
+                    ids.to(self.device), offs.to(self.device), w
+                ).to(torch.float32)
+            if mode == "mean":
+                lens = offs.diff().clamp_(min=1).to(self.device)
+                out = out / lens.to(torch.float32).unsqueeze(1)
+        return out
+
+    def _pool_exchange(self, ids: torch.Tensor, offs: torch.Tensor,
+                       w: Optional[torch.Tensor]):
+        """Sync plane: my parts to their owners, one pooled row per part
+        back. Returns ``[(bag index of each part, its rows)]`` per server."""
+        plan = plan_bags(ids, offs, self.spec)
+        in_ids, in_offs, in_w, recv_parts = all_to_all_bags(
+            ids, w, plan, self.device)
+        served = self._server_pool(self._local_rows_of(in_ids), in_offs, in_w)
+        got = all_to_all_values(served.view(-1), recv_parts, plan.n_parts,
+                                self.num_col).view(-1, self.num_col)
+        return list(zip(plan.part_bag.split(plan.n_parts),
+                        got.split(plan.n_parts)))
+
+    def _pool_merge(self, n_bags: int, parts) -> torch.Tensor:
+        """The owners' partials added in server order into a zeroed fp32
+        buffer. The bag indices of one server's parts are distinct, so an
+        ``index_add_`` has no colliding adds."""
+        out = torch.zeros(n_bags, self.num_col, dtype=torch.float32,
+                          device=self.device)
+        for bags, rows in parts:
+            if bags.numel():
+                out.index_add_(0, bags.to(self.device),
+                               rows.to(self.device, torch.float32))
+        return out
+
+    def _server_pool(self, local_ids: torch.Tensor, offsets: torch.Tensor,
+                     weights: Optional[torch.Tensor]) -> torch.Tensor:
+        """The one server-side entry of pool_rows, for the local path and
+        both planes: the pooled rows ``[B, num_col]`` of the bags
+        ``local_ids[offsets[b]:offsets[b+1]]`` (int64 local row ids and CSR
+        offsets, fp32 weights or None, all on the table's device), in the
+        table's wire dtype. k_row_pool on a float32 GPU shard; torch ops on
+        the CPU and for float64."""
+        with self._shard_lock, monitor("server.pool_rows"):
+            if self.shard.is_cuda and self.dtype == torch.float32:
+                from .. import ops
+                hip = ops.module(required=True)
+                return hip.row_pool(
+                    self.shard, local_ids.contiguous(), offsets.contiguous(),
+                    weights, self.wire if self.wire != self.dtype else None)
+            n_bags = offsets.numel() - 1
+            vals = self.shard[local_ids]
+            if weights is not None:
+                vals = vals * weights.to(self.dtype).unsqueeze(1)
+            bag_of = torch.repeat_interleave(
+                torch.arange(n_bags, device=vals.device), offsets.diff())
+            out = torch.zeros(n_bags, self.num_col, dtype=self.dtype,
+                              device=vals.device)
+            return out.index_add_(0, bag_of, vals).to(self.wire)
 
     # ---- checkpoint (matrix_table.cpp:457-464) ----
     def store(self, path: str) -> None:
