@@ -66,6 +66,11 @@ OP_NEAREST = 10     # nearest_rows: payload = Q fp32 queries of num_col;
 OP_POOL_ROWS = 11   # pool_rows: one blob [ids: n_keys i64][part lengths:
                     # n_vals i64][weights: n_keys fp32 if has_opt]; reply =
                     # n_vals pooled rows of num_col in the wire dtype
+OP_ADD_POOLED = 12  # add_pooled: one blob [opt: 5 f64 if has_opt][ids: n_keys
+                    # i64][part lengths: n_vals i64][weights: n_keys fp32,
+                    # padded to 8 bytes, if want_ack][n_vals gradient rows of
+                    # num_col in the wire dtype]. The op has no reply, so the
+                    # want_ack field says "weighted"
 
 _HDR = 6  # int64 fields: [op, table_id, n_keys, n_vals, want_ack, has_opt]
 
@@ -393,6 +398,52 @@ class AsyncEngine:
             wk.wait()
         return parts
 
+    def pooled_add(self, table, ids_cpu: torch.Tensor,
+                   weights: Optional[torch.Tensor], vals: torch.Tensor, plan,
+                   option: Optional[AddOption]):
+        """add_pooled: every server that owns some of the ids gets them with
+        their part lengths and weights, as for ``pool``, and ONE gradient row
+        per part (``vals`` is ``[B, num_col]`` in the wire dtype, gathered by
+        the parts' bag indices). The server rebuilds each row's gradient and
+        steps its updater on arrival. The local shard is served without the
+        transport, and a server that owns none of the ids gets no message."""
+        zoo = self.zoo
+        sorted_ids = ids_cpu[plan.order]
+        sorted_w = (None if weights is None
+                    else weights[plan.order.to(weights.device)])
+        opt = _opt_tensor(option)
+        works: List = []
+        refs: List = []
+        id0 = part0 = 0
+        for s, (cnt, np_) in enumerate(zip(plan.n_ids, plan.n_parts)):
+            if cnt == 0:
+                continue
+            dst = zoo.server_ranks[s]
+            keys = sorted_ids[id0:id0 + cnt]
+            lens = plan.part_len[part0:part0 + np_]
+            piece = vals[plan.part_bag[part0:part0 + np_].to(vals.device)]
+            w = None if sorted_w is None else sorted_w[id0:id0 + cnt]
+            id0 += cnt
+            part0 += np_
+            if dst == zoo.rank:
+                table._server_add_pooled(
+                    (keys - table.row_offset).to(table.device),
+                    csr_of(lens).to(table.device), piece, w, option)
+                continue
+            hdr = [OP_ADD_POOLED, table.table_id, cnt, np_,
+                   0 if w is None else 1, 0 if opt is None else 1]
+            ps = ([] if opt is None else [opt]) + [keys.contiguous(),
+                                                   lens.contiguous()]
+            if w is not None:
+                wpad = torch.zeros(cnt + (cnt & 1), dtype=torch.float32)
+                wpad[:cnt] = w
+                ps.append(wpad)
+            ps.append(piece.reshape(-1).cpu().contiguous())
+            wk, r = self._send_request(dst, hdr, ps)
+            works += wk
+            refs += r
+        return PendingReply(works, refs)
+
     def kv_add(self, table, keys: torch.Tensor, vals: torch.Tensor):
         """KVTable add: key % num_servers sharding (kv_table.h:49)."""
         zoo = self.zoo
@@ -606,6 +657,29 @@ class AsyncEngine:
                     (keys - table.row_offset).to(table.device),
                     csr_of(lens).to(table.device), w)
             dist.send(got.cpu().contiguous(), src, group=self.rep)
+            return
+        if op == OP_ADD_POOLED:
+            # n_keys = ids (> 0), n_vals = parts, want_ack = weighted
+            at = 40 if has_opt else 0
+            w_at = at + (n_keys + n_vals) * 8
+            v_at = w_at + ((n_keys + 1) // 2 * 8 if want_ack else 0)
+            blob = torch.empty(
+                v_at + n_vals * table.num_col
+                * torch.empty(0, dtype=table.wire).element_size(),
+                dtype=torch.uint8)
+            dist.recv(blob, src, group=self.req)
+            option = _opt_from(blob[:40].view(torch.float64)) if has_opt \
+                else None
+            keys = blob[at:at + n_keys * 8].view(torch.int64)
+            lens = blob[at + n_keys * 8:w_at].view(torch.int64)
+            w = (blob[w_at:w_at + n_keys * 4].view(torch.float32)
+                 .to(table.device) if want_ack else None)
+            with monitor("server.process_add"):
+                table._server_add_pooled(
+                    (keys - table.row_offset).to(table.device),
+                    csr_of(lens).to(table.device),
+                    blob[v_at:].view(table.wire).view(n_vals, -1)
+                    .to(table.device), w, option)
             return
         # One blob recv mirrors the worker's one blob send (layout in
         # _send_request: [opt][keys][vals], 8-byte aligned sections)

@@ -15,7 +15,9 @@ MI355X-native mapping (BASELINE.json north star):
   point-to-point links far better than a ring of small messages
 - pooled row Get (``pool_rows``) = the same keyed all-to-all, but a bag's
   ids travel with their part lengths (``plan_bags``, ``all_to_all_bags``) and
-  one pooled row per bag and owner comes back instead of one row per id
+  one pooled row per bag and owner comes back instead of one row per id;
+  the pooled Add (``add_pooled``, ``all_to_all_bag_values``) sends one
+  gradient row per bag and owner the same way, with no reply
 - aggregate (MV_Aggregate / -ma mode) = one all-reduce
 - bf16 wire format (tables built with ``wire_dtype=torch.bfloat16``): the
   same collectives carry bfloat16 payloads for an fp32 shard. Nothing here is
@@ -402,6 +404,27 @@ def all_to_all_bags(ids_cpu: torch.Tensor, weights: Optional[torch.Tensor],
         in_w = all_to_all_values(weights[plan.order.to(device)], plan.n_ids,
                                  recv_ids, 1)
     return in_ids, csr_of(in_lens), in_w, recv_parts
+
+
+def all_to_all_bag_values(ids_cpu: torch.Tensor,
+                          weights: Optional[torch.Tensor],
+                          bag_values: torch.Tensor, plan: BagPlan,
+                          device: torch.device
+                          ) -> Tuple[torch.Tensor, torch.Tensor,
+                                     Optional[torch.Tensor], torch.Tensor]:
+    """A pooled Add on the sync plane: ``all_to_all_bags`` plus the values.
+    ``bag_values`` is ``[B, unit]`` in the wire dtype on ``device``; it is
+    gathered once by ``plan.part_bag``, so ONE gradient row per part travels
+    (splits ``n_parts * unit``) instead of one per id. Returns ``(in_ids,
+    in_offsets, in_weights, in_vals)``, ``in_vals`` being ``[parts, unit]`` in
+    the order of the CSR's parts. There is no reply."""
+    unit = bag_values.size(1)
+    in_ids, in_offs, in_w, recv_parts = all_to_all_bags(ids_cpu, weights,
+                                                        plan, device)
+    in_vals = all_to_all_values(
+        bag_values[plan.part_bag.to(device)].reshape(-1), plan.n_parts,
+        recv_parts, unit)
+    return in_ids, in_offs, in_w, in_vals.view(-1, unit)
 
 
 def all_to_all_values(values: torch.Tensor, send_sizes: List[int],

@@ -569,6 +569,113 @@ void row_adam_update(torch::Tensor shard, torch::Tensor m, torch::Tensor v,
                      eps, rows.numel(), shard.size(1), cur_stream());
 }
 
+// Pooled Add (k_row_unpool): the validation shared by the unpool_X_update
+// entry points, which returns the launchers' list. vals is [P, cols], fp32 or
+// bf16; rows holds the sorted local ids, perm the caller's position of each;
+// src (the row of vals) and weights are in caller order. What rows, perm and
+// src hold lies in device memory and is not checked here (that would take a
+// sync): P is declared by vals' first dimension, and the caller builds src
+// from its part lengths.
+MvUnpool check_unpool(const torch::Tensor& shard,
+                      std::initializer_list<Named> state,
+                      const torch::Tensor& rows, const torch::Tensor& perm,
+                      const torch::Tensor& src, const torch::Tensor& vals,
+                      const c10::optional<torch::Tensor>& weights) {
+  check_f32(shard, "shard");
+  TORCH_CHECK(shard.dim() == 2 && shard.size(1) >= 1,
+              "shard must be 2-D with at least one column");
+  for (const auto& t : state) {
+    check_f32(t.second, t.first);
+    TORCH_CHECK(t.second.sizes() == shard.sizes(), t.first,
+                " shape mismatch");
+  }
+  check_dev(rows, "rows", torch::kInt64);
+  check_dev(perm, "perm", torch::kInt64);
+  check_dev(src, "src", torch::kInt64);
+  int64_t n = rows.numel();
+  TORCH_CHECK(perm.numel() == n, "perm size mismatch");
+  TORCH_CHECK(src.numel() == n, "src size mismatch");
+  TORCH_CHECK(vals.dim() == 2 && vals.size(1) == shard.size(1),
+              "vals must be [P, ", shard.size(1), "]");
+  int wire = wire_bit(vals, "vals", vals.numel(), kWireDelta);
+  TORCH_CHECK(n <= INT32_MAX && vals.size(0) <= INT32_MAX,
+              "a pooled Add takes fewer than 2^31 ids and parts");
+  TORCH_CHECK(n == 0 || (vals.size(0) >= 1 && shard.size(0) >= 1),
+              "ids into an empty shard or without gradient rows");
+  const float* wts = nullptr;
+  if (weights.has_value()) {
+    check_f32(*weights, "weights");
+    TORCH_CHECK(weights->numel() == n, "weights size mismatch");
+    wts = f32(*weights);
+  }
+  return MvUnpool{vals.data_ptr(), wire, rows.data_ptr<int64_t>(),
+                  perm.data_ptr<int64_t>(), src.data_ptr<int64_t>(), wts, n,
+                  shard.size(1)};
+}
+
+using OptTensor = c10::optional<torch::Tensor>;
+
+template <int SIGN>
+void unpool_sgd_update(torch::Tensor shard, torch::Tensor rows,
+                       torch::Tensor perm, torch::Tensor src,
+                       torch::Tensor vals, OptTensor weights) {
+  MvUnpool a = check_unpool(shard, {}, rows, perm, src, vals, weights);
+  mv_launch_unpool_sgd(f32(shard), (float)SIGN, &a, cur_stream());
+}
+
+void unpool_adagrad_update(torch::Tensor shard, torch::Tensor gsq,
+                           torch::Tensor rows, torch::Tensor perm,
+                           torch::Tensor src, torch::Tensor vals,
+                           OptTensor weights, double lr, double rho,
+                           double eps) {
+  MvUnpool a = check_unpool(shard, {{"gsq", gsq}}, rows, perm, src, vals,
+                            weights);
+  mv_launch_unpool_adagrad(f32(shard), f32(gsq), (float)lr, (float)rho,
+                           (float)eps, &a, cur_stream());
+}
+
+void unpool_momentum_update(torch::Tensor shard, torch::Tensor m,
+                            torch::Tensor rows, torch::Tensor perm,
+                            torch::Tensor src, torch::Tensor vals,
+                            OptTensor weights, double mu) {
+  MvUnpool a = check_unpool(shard, {{"m", m}}, rows, perm, src, vals,
+                            weights);
+  mv_launch_unpool_momentum(f32(shard), f32(m), (float)mu, &a, cur_stream());
+}
+
+void unpool_dcasgd_update(torch::Tensor shard, torch::Tensor bak,
+                          torch::Tensor rows, torch::Tensor perm,
+                          torch::Tensor src, torch::Tensor vals,
+                          OptTensor weights, double lr, double lambda) {
+  MvUnpool a = check_unpool(shard, {{"bak", bak}}, rows, perm, src, vals,
+                            weights);
+  mv_launch_unpool_dcasgd(f32(shard), f32(bak), (float)lr, (float)lambda, &a,
+                          cur_stream());
+}
+
+void unpool_dcasgda_update(torch::Tensor shard, torch::Tensor bak,
+                           torch::Tensor msq, torch::Tensor rows,
+                           torch::Tensor perm, torch::Tensor src,
+                           torch::Tensor vals, OptTensor weights, double lr,
+                           double lambda, double rho, double eps) {
+  MvUnpool a = check_unpool(shard, {{"bak", bak}, {"msq", msq}}, rows, perm,
+                            src, vals, weights);
+  mv_launch_unpool_dcasgda(f32(shard), f32(bak), f32(msq), (float)lr,
+                           (float)lambda, (float)rho, (float)eps, &a,
+                           cur_stream());
+}
+
+void unpool_adam_update(torch::Tensor shard, torch::Tensor m, torch::Tensor v,
+                        torch::Tensor rows, torch::Tensor perm,
+                        torch::Tensor src, torch::Tensor vals,
+                        OptTensor weights, double b1, double b2, double step,
+                        double rbc2, double decay, double eps) {
+  MvUnpool a = check_unpool(shard, {{"m", m}, {"v", v}}, rows, perm, src,
+                            vals, weights);
+  mv_launch_unpool_adam(f32(shard), f32(m), f32(v), b1, b2, step, rbc2, decay,
+                        eps, &a, cur_stream());
+}
+
 void w2v_train(torch::Tensor in_emb, torch::Tensor out_emb,
                torch::Tensor in_gsq, torch::Tensor out_gsq,
                torch::Tensor in_idx, torch::Tensor in_off,
@@ -1158,6 +1265,43 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("vals"), py::arg("b1"), py::arg("b2"), py::arg("step"),
         py::arg("rbc2"), py::arg("decay"), py::arg("eps"),
         py::arg("perm") = py::none());
+  m.def("unpool_default_update", &unpool_sgd_update<1>,
+        "pooled Add: row rows[k] += the sum over its run of equal ids of "
+        "weights[p] * vals[src[p]], p = perm[k], in list order (rows sorted, "
+        "perm its stable sort; src and weights in caller order; vals [P, "
+        "cols] fp32 or bf16)",
+        py::arg("shard"), py::arg("rows"), py::arg("perm"), py::arg("src"),
+        py::arg("vals"), py::arg("weights") = py::none());
+  m.def("unpool_sgd_update", &unpool_sgd_update<-1>,
+        "pooled sgd: unpool_default_update with the sum subtracted",
+        py::arg("shard"), py::arg("rows"), py::arg("perm"), py::arg("src"),
+        py::arg("vals"), py::arg("weights") = py::none());
+  m.def("unpool_adagrad_update", &unpool_adagrad_update,
+        "pooled adagrad: one step per distinct row on the sum of "
+        "unpool_default_update",
+        py::arg("shard"), py::arg("gsq"), py::arg("rows"), py::arg("perm"),
+        py::arg("src"), py::arg("vals"), py::arg("weights"), py::arg("lr"),
+        py::arg("rho"), py::arg("eps"));
+  m.def("unpool_momentum_update", &unpool_momentum_update,
+        "pooled momentum, the contract of unpool_adagrad_update",
+        py::arg("shard"), py::arg("m"), py::arg("rows"), py::arg("perm"),
+        py::arg("src"), py::arg("vals"), py::arg("weights"), py::arg("mu"));
+  m.def("unpool_dcasgd_update", &unpool_dcasgd_update,
+        "pooled DC-ASGD, the contract of unpool_adagrad_update",
+        py::arg("shard"), py::arg("bak"), py::arg("rows"), py::arg("perm"),
+        py::arg("src"), py::arg("vals"), py::arg("weights"), py::arg("lr"),
+        py::arg("lam"));
+  m.def("unpool_dcasgda_update", &unpool_dcasgda_update,
+        "pooled DC-ASGD-a, the contract of unpool_adagrad_update",
+        py::arg("shard"), py::arg("bak"), py::arg("msq"), py::arg("rows"),
+        py::arg("perm"), py::arg("src"), py::arg("vals"), py::arg("weights"),
+        py::arg("lr"), py::arg("lam"), py::arg("rho"), py::arg("eps"));
+  m.def("unpool_adam_update", &unpool_adam_update,
+        "pooled Adam, the contract of unpool_adagrad_update",
+        py::arg("shard"), py::arg("m"), py::arg("v"), py::arg("rows"),
+        py::arg("perm"), py::arg("src"), py::arg("vals"), py::arg("weights"),
+        py::arg("b1"), py::arg("b2"), py::arg("step"), py::arg("rbc2"),
+        py::arg("decay"), py::arg("eps"));
   m.def("row_topk", &row_topk,
         "nearest rows: (scores [Q,k], global ids [Q,k]) of the k best shard "
         "rows per query, dot or cosine; None when one query exceeds the LDS "

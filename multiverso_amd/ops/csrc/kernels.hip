@@ -213,10 +213,11 @@ static inline int grid_for(int64_t work_items) {
 // D is the delta's element type: T, or bf16 on an fp32 shard (widened by ld).
 // Every step issues all its loads before its first store: struct members
 // carry no __restrict__, so a load written after a store would wait for it.
-// The momentum, DC-ASGD and Adam ops keep their formula in
-// step_at<V>(i, g), which takes the gradient as a value (step loads it from
-// delta first): the row-keyed k_row_update below hands it a per-row sum
-// instead.
+// Every op has a step_at<V>(i, g), which takes the gradient as a value: the
+// row-keyed k_row_update and k_row_unpool below hand it a per-row sum. The
+// momentum, DC-ASGD and Adam ops keep their formula there (step loads the
+// gradient from delta first); the add, sgd and adagrad ops keep step's own
+// order of loads, shard first, so step_at stands beside step.
 // ---------------------------------------------------------------------------
 
 template <class T, class D = T>
@@ -225,6 +226,12 @@ struct AddOp {
   T* data; const D* delta;
   template <class V> __device__ __forceinline__ V step(int64_t i) const {
     V v = ld_shard<V, true>(data, i) + ld<V>(delta, i);
+    st(data, i, v);
+    return v;
+  }
+  template <class V>
+  __device__ __forceinline__ V step_at(int64_t i, V g) const {
+    V v = ld_shard<V, false>(data, i) + g;
     st(data, i, v);
     return v;
   }
@@ -238,6 +245,12 @@ struct SgdOp {
   T* data; const D* delta; T sign;
   template <class V> __device__ __forceinline__ V step(int64_t i) const {
     V v = ld_shard<V, true>(data, i) + sign * ld<V>(delta, i);
+    st(data, i, v);
+    return v;
+  }
+  template <class V>
+  __device__ __forceinline__ V step_at(int64_t i, V g) const {
+    V v = ld_shard<V, false>(data, i) + sign * g;
     st(data, i, v);
     return v;
   }
@@ -268,9 +281,10 @@ template <class T, class D = T>
 struct AdagradOp {
   using elem = T;
   T* data; T* gsq; const D* delta; T inv_lr, rho, eps;
-  template <class V> __device__ __forceinline__ V step(int64_t i) const {
-    V d = ld_shard<V, true>(data, i), G = ld<V>(gsq, i);
-    V g = ld<V>(delta, i) * inv_lr;
+  // d and G as loaded, g the raw gradient
+  template <class V>
+  __device__ __forceinline__ V finish(int64_t i, V d, V G, V g) const {
+    g = g * inv_lr;
     G += g * g;
     // double keeps the exact divide; fp32 uses the hardware rsq
     if constexpr (std::is_same<T, double>::value) d -= rho * g / sqrt(G + eps);
@@ -278,6 +292,15 @@ struct AdagradOp {
     st(gsq, i, G);
     st(data, i, d);
     return d;
+  }
+  template <class V> __device__ __forceinline__ V step(int64_t i) const {
+    V d = ld_shard<V, true>(data, i), G = ld<V>(gsq, i);
+    return finish(i, d, G, ld<V>(delta, i));
+  }
+  template <class V>
+  __device__ __forceinline__ V step_at(int64_t i, V g) const {
+    V d = ld_shard<V, false>(data, i), G = ld<V>(gsq, i);
+    return finish(i, d, G, g);
   }
 };
 
@@ -2783,21 +2806,40 @@ static __device__ __forceinline__ v4f pool_step(v4f acc, v4f x, float w,
   return r;
 }
 
+// vector i of the matrix whose rows are summed, viewed as V: a plain load
+// (rows repeat, the caches help); a bf16 matrix widens in registers
+template <class V>
+static __device__ __forceinline__ V pool_ld(const float* p, int64_t i) {
+  return ((const V*)p)[i];
+}
+template <class V>
+static __device__ __forceinline__ V pool_ld(const bf16* p, int64_t i) {
+  if constexpr (std::is_same<V, v4f>::value) {
+    v4h h = ((const v4h*)p)[i];
+    v4f v;
+    v.x = widen(h.x); v.y = widen(h.y); v.z = widen(h.z); v.w = widen(h.w);
+    return v;
+  } else {
+    return widen(p[i].bits);
+  }
+}
+
 // N staged items, t .. t+N-1 of the round held in (rid, w) across the group's
 // lanes; item t+u belongs to the bag while t + u < left. All N * VPL loads
-// are issued before the first add.
-template <int G, int VPL, int N, bool WEIGHTED, class V>
+// are issued before the first add. mat is the shard (k_row_pool) or the
+// gradient matrix (k_row_unpool), rid the row of mat an item names.
+template <int G, int VPL, int N, bool WEIGHTED, class V, class D>
 static __device__ __forceinline__ void pool_items(
-    V (&acc)[VPL], const V* __restrict__ shard, int vcols,
+    V (&acc)[VPL], const D* __restrict__ mat, int vcols,
     const int (&col)[VPL], int64_t rid, float w, int t, int left) {
   V x[N][VPL];
   float wv[N];
 #pragma unroll
   for (int u = 0; u < N; ++u) {
-    const V* row = shard + pool_bcast<G>(rid, t + u) * (int64_t)vcols;
+    const int64_t row = pool_bcast<G>(rid, t + u) * (int64_t)vcols;
     wv[u] = WEIGHTED ? pool_bcast<G>(w, t + u) : 0.f;
 #pragma unroll
-    for (int r = 0; r < VPL; ++r) x[u][r] = row[col[r]];
+    for (int r = 0; r < VPL; ++r) x[u][r] = pool_ld<V>(mat, row + col[r]);
   }
 #pragma unroll
   for (int u = 0; u < N; ++u) {
@@ -2850,11 +2892,11 @@ __global__ __launch_bounds__(BLOCK) void k_row_pool(
       const int cnt = min(G, longest - base), left = len - base;
       int t = 0;
       for (; t + U <= cnt; t += U)
-        pool_items<G, VPL, U, WEIGHTED>(acc, shard, vcols, col, rid, w, t,
-                                        left);
+        pool_items<G, VPL, U, WEIGHTED>(acc, (const float*)shard, vcols, col,
+                                        rid, w, t, left);
       for (; t < cnt; ++t)
-        pool_items<G, VPL, 1, WEIGHTED>(acc, shard, vcols, col, rid, w, t,
-                                        left);
+        pool_items<G, VPL, 1, WEIGHTED>(acc, (const float*)shard, vcols, col,
+                                        rid, w, t, left);
     }
 #pragma unroll
     for (int r = 0; r < VPL; ++r)
@@ -2916,6 +2958,217 @@ extern "C" void mv_launch_row_pool(void* out, int wire, const float* shard,
     launch_row_pool(o, shard, rows, offsets, wts, B, cols, s);
   });
 }
+
+// ---------------------------------------------------------------------------
+// Pooled Add (MatrixTable.add_pooled, the embedding-bag backward): k_row_pool
+// turned round. The gradient of a pooled read hands row r the sum over the
+// list positions i that name r of w_i * vals[src_i], where vals holds ONE
+// gradient row per bag part and src_i is the part of position i. A run of
+// equal row ids is therefore a bag over the small matrix vals: it is summed in
+// registers and the updater steps once per distinct row (Op::step_at, the
+// keyed semantics of k_row_update), so the expanded nnz x cols rows never
+// exist.
+//
+// k_row_unpool<Op, G, VPL, V, D, WEIGHTED>: rows[n] are the sorted local ids,
+// perm[k] the caller's position of sorted position k; src[n] (and wts[n]) are
+// in caller order and read through perm. Geometry is with_pool_shape's: a run
+// is served by a group of G lanes, lane j keeping VPL column vectors of the
+// sum, wide rows in panels over gridDim.y. D is vals' type, float or bf16
+// (widened by pool_ld; the sums stay fp32).
+//
+// Runs are found without a segment table: a wave takes windows of 64
+// consecutive list positions (grid-stride), loads their ids with one
+// coalesced load, and the ballot of `id != predecessor's id` is the window's
+// head mask (lane 0 looks at rows[base - 1]). The wave's 64 / G groups take
+// the set bits in order, 64 / G a round, so all groups work while the window
+// has heads, and a window inside one long run costs that one load.
+//
+// A head group walks its run G list positions a round, lane j staging
+// (rows, perm -> src, wts) of position start + G*k + j. The ids are sorted,
+// so the positions that still carry the run's id are a prefix of the round
+// and a ballot inside the group counts them; the walk goes on while a whole
+// round was live. Every loop bound is wave-uniform (the longest run, the
+// fullest round of the wave's groups). A group past its end, or without a
+// head, stages a clamped, valid position and pool_items drops it by a select,
+// never a multiply by zero: an inf gradient row reaches only the rows whose
+// runs list it.
+//
+// Ordering contract: a row's contributions are added in caller order (the
+// sort is stable) from +0.0, acc + x or fmaf(w, x, acc), by one lane per
+// column: repeatable bit for bit, independent of the grid. No atomics, LDS
+// or scratch; 64-bit addresses. Known limit, as in k_row_update: one group
+// walks a run serially.
+// ---------------------------------------------------------------------------
+
+// n >= 1 list positions; vcols counts V's per row
+template <class Op, int G, int VPL, class V, class D, bool WEIGHTED>
+__global__ __launch_bounds__(BLOCK) void k_row_unpool(
+    Op op, const D* __restrict__ vals, const int64_t* __restrict__ rows,
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ src,
+    const float* __restrict__ wts, int n, int vcols) {
+  constexpr int U = pool_u(VPL), GPW = WAVE / G;
+  constexpr uint64_t GMASK = G == WAVE ? ~0ull : (1ull << (G & 63)) - 1;
+  const int lane = threadIdx.x & 63, j = lane & (G - 1), grp = lane / G;
+  const int wave = __builtin_amdgcn_readfirstlane(
+      (int)((blockIdx.x * BLOCK + threadIdx.x) >> 6));
+  const int nwaves = gridDim.x * (BLOCK / WAVE);
+  int col[VPL];
+  bool own[VPL];
+#pragma unroll
+  for (int r = 0; r < VPL; ++r) {
+    int c = blockIdx.y * (G * VPL) + j + G * r;
+    own[r] = c < vcols;
+    col[r] = own[r] ? c : vcols - 1;
+  }
+  for (int64_t base = (int64_t)wave * WAVE; base < n;
+       base += (int64_t)nwaves * WAVE) {
+    const int64_t pos = base + lane;
+    const int64_t id = rows[pos < n ? pos : n - 1];
+    int64_t before = __shfl_up(id, 1, WAVE);
+    if (lane == 0) before = base > 0 ? rows[base - 1] : ~id;
+    uint64_t heads = __ballot(pos < n && id != before);
+    while (heads) {
+      // the next GPW heads of the window, one for each group
+      int bit = -1;
+#pragma unroll
+      for (int g = 0; g < GPW; ++g) {
+        int b = heads ? __builtin_ctzll(heads) : -1;
+        heads &= heads - 1;
+        bit = grp == g ? b : bit;
+      }
+      const bool head = bit >= 0;
+      const int64_t start = head ? base + bit : 0;
+      const int64_t run = rows[start];
+      V acc[VPL];
+#pragma unroll
+      for (int r = 0; r < VPL; ++r) acc[r] = V{};
+      bool walking = head;
+      for (int64_t k = start;; k += G) {
+        const int64_t at = k + j, atc = at < n ? at : n - 1;
+        const bool live = walking && at < n && rows[atc] == run;
+        const int left = __popcll((__ballot(live) >> (lane - j)) & GMASK);
+        const int64_t p = perm[atc];
+        const int64_t sid = src[p];
+        const float w = WEIGHTED ? wts[p] : 0.f;
+        int cnt = left;
+#pragma unroll
+        for (int sh = G; sh < WAVE; sh <<= 1)
+          cnt = max(cnt, __shfl_xor(cnt, sh, WAVE));
+        cnt = __builtin_amdgcn_readfirstlane(cnt);
+        int t = 0;
+        for (; t + U <= cnt; t += U)
+          pool_items<G, VPL, U, WEIGHTED>(acc, vals, vcols, col, sid, w, t,
+                                          left);
+        for (; t < cnt; ++t)
+          pool_items<G, VPL, 1, WEIGHTED>(acc, vals, vcols, col, sid, w, t,
+                                          left);
+        walking = walking && left == G;
+        if (!__any(walking)) break;
+      }
+#pragma unroll
+      for (int r = 0; r < VPL; ++r)
+        if (head && own[r])
+          op.template step_at<V>(run * vcols + col[r], acc[r]);
+    }
+  }
+}
+
+// `vec` (every pointer of the op 16-byte aligned) with cols % 4 == 0 and
+// vals' own alignment selects V = v4f; everything else takes the scalar form
+// of the same source. n is below 2^31 (the binding refuses more).
+template <class Op, class D>
+static void launch_row_unpool(const Op& op, bool vec, const D* vals,
+                              const MvUnpool& a, hipStream_t s) {
+  if (!a.n || !a.cols) return;
+  vec = vec && a.cols % 4 == 0 && vals_vec_ok(vals);
+  int64_t vcols = vec ? a.cols / 4 : a.cols;
+  with_pool_shape(vcols, [&](auto g, auto v) {
+    constexpr int G = decltype(g)::value, VPL = decltype(v)::value;
+    int64_t panel = G * VPL;
+    dim3 grid((unsigned)grid_for_cap(a.n, POOL_GRID),
+              (unsigned)((vcols + panel - 1) / panel));
+    auto go = [&](auto vtag) {
+      using V = decltype(vtag);
+      if (a.wts)
+        k_row_unpool<Op, G, VPL, V, D, true><<<grid, BLOCK, 0, s>>>(
+            op, vals, a.rows, a.perm, a.src, a.wts, (int)a.n, (int)vcols);
+      else
+        k_row_unpool<Op, G, VPL, V, D, false><<<grid, BLOCK, 0, s>>>(
+            op, vals, a.rows, a.perm, a.src, a.wts, (int)a.n, (int)vcols);
+    };
+    if (vec) go(v4f{});
+    else go(0.f);
+  });
+}
+
+// f(vals) with the list's gradient matrix cast to what a.wire says it holds
+template <class F>
+static void with_unpool_vals(const MvUnpool& a, F f) {
+  with_wire(a.wire, a.vals, nullptr, [&](auto* x, auto*) { f(x); });
+}
+
+extern "C" {
+
+// sign = +1 is the default (add) updater, -1 is sgd
+void mv_launch_unpool_sgd(float* shard, float sign, const MvUnpool* a,
+                          hipStream_t s) {
+  with_unpool_vals(*a, [&](auto* x) {
+    launch_row_unpool(SgdOp<float>{shard, nullptr, sign}, aligned16(shard), x,
+                      *a, s);
+  });
+}
+
+void mv_launch_unpool_adagrad(float* shard, float* gsq, float lr, float rho,
+                              float eps, const MvUnpool* a, hipStream_t s) {
+  bool vec = aligned16(shard) && aligned16(gsq);
+  with_unpool_vals(*a, [&](auto* x) {
+    launch_row_unpool(AdagradOp<float>{shard, gsq, nullptr, 1.0f / lr, rho,
+                                       eps},
+                      vec, x, *a, s);
+  });
+}
+
+void mv_launch_unpool_momentum(float* shard, float* m, float mu,
+                               const MvUnpool* a, hipStream_t s) {
+  bool vec = aligned16(shard) && aligned16(m);
+  with_unpool_vals(*a, [&](auto* x) {
+    launch_row_unpool(MomentumOp<float>{shard, m, nullptr, mu}, vec, x, *a,
+                      s);
+  });
+}
+
+void mv_launch_unpool_dcasgd(float* shard, float* bak, float lr, float lambda,
+                             const MvUnpool* a, hipStream_t s) {
+  bool vec = aligned16(shard) && aligned16(bak);
+  with_unpool_vals(*a, [&](auto* x) {
+    launch_row_unpool(DcasgdOp<float>{shard, bak, nullptr, lr, lambda}, vec,
+                      x, *a, s);
+  });
+}
+
+void mv_launch_unpool_dcasgda(float* shard, float* bak, float* msq, float lr,
+                              float lambda, float rho, float eps,
+                              const MvUnpool* a, hipStream_t s) {
+  bool vec = aligned16(shard) && aligned16(bak) && aligned16(msq);
+  with_unpool_vals(*a, [&](auto* x) {
+    launch_row_unpool(DcasgdaOp<float>{shard, bak, msq, nullptr, lr, lambda,
+                                       rho, eps},
+                      vec, x, *a, s);
+  });
+}
+
+void mv_launch_unpool_adam(float* shard, float* m, float* v, double b1,
+                           double b2, double step, double rbc2, double decay,
+                           double eps, const MvUnpool* a, hipStream_t s) {
+  bool vec = aligned16(shard) && aligned16(m) && aligned16(v);
+  with_unpool_vals(*a, [&](auto* x) {
+    launch_row_unpool(adam_op<float, float>(shard, m, v, nullptr, b1, b2,
+                                            step, rbc2, decay, eps),
+                      vec, x, *a, s);
+  });
+}
+
+}  // extern "C"
 
 // ---------------------------------------------------------------------------
 // Nearest rows (MatrixTable.nearest_rows): the k best rows of the shard for

@@ -8,6 +8,21 @@
 #include <hip/hip_runtime_api.h>
 #include <cstdint>
 
+// The list of a pooled Add, the same for every updater: vals [P, cols] holds
+// fp32, or bf16 when wire has WIRE_DELTA; rows [n] are the sorted local ids,
+// perm [n] the caller's position of each; src [n] (the row of vals, below P)
+// and wts [n] (or null) are in caller order. n and P are below 2^31; n == 0
+// launches nothing.
+struct MvUnpool {
+  const void* vals;
+  int wire;
+  const int64_t* rows;
+  const int64_t* perm;
+  const int64_t* src;
+  const float* wts;
+  int64_t n, cols;
+};
+
 extern "C" {
 // elementwise updaters: a non-null `out` (the pointer before `wire`)
 // selects the fused Add+Get form. The fp32 forms take the delta and `out`
@@ -95,6 +110,21 @@ void mv_launch_row_adam(float*, float*, float*, const void*, int,
                         const int64_t*, const int64_t*, double, double,
                         double, double, double, double, int64_t, int64_t,
                         hipStream_t);
+// pooled Add (k_row_unpool): (shard, state..., scalars..., list). Row
+// rows[k] of the shard gets the sum of weights[p] * vals[src[p]] over its run
+// of equal ids, p = perm[k], in list order, then one updater step.
+void mv_launch_unpool_sgd(float*, float, const MvUnpool*, hipStream_t);
+void mv_launch_unpool_adagrad(float*, float*, float, float, float,
+                              const MvUnpool*, hipStream_t);
+void mv_launch_unpool_momentum(float*, float*, float, const MvUnpool*,
+                               hipStream_t);
+void mv_launch_unpool_dcasgd(float*, float*, float, float, const MvUnpool*,
+                             hipStream_t);
+void mv_launch_unpool_dcasgda(float*, float*, float*, float, float, float,
+                              float, const MvUnpool*, hipStream_t);
+void mv_launch_unpool_adam(float*, float*, float*, double, double, double,
+                           double, double, double, const MvUnpool*,
+                           hipStream_t);
 // word2vec: (in_emb, out_emb, in_gsq, out_gsq, in_idx, in_off, ...,
 // groups, dim, use_adagrad, use_atomic)
 void mv_launch_w2v(float*, float*, float*, float*, const int64_t*, const int*,

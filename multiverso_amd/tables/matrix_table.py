@@ -50,6 +50,11 @@ MI355X mapping:
   touches crosses the wire instead of one per id; the caller adds the owners'
   partials in server order.
 
+- ``add_pooled`` = its backward: one gradient row per bag and owner crosses
+  the wire, each owner sums for every row the contributions of the ids that
+  name it (k_row_unpool, runs of the sorted ids) and steps its updater once
+  per distinct row, so the ``nnz x num_col`` expanded rows never exist.
+
 Sparse/stale-aware Get (SparseMatrixTable's per-(worker,row) freshness
 bitmap) is implemented in sparse_matrix.py on top of this class; it takes no
 ``wire_dtype``.
@@ -61,8 +66,9 @@ from typing import Optional, Tuple
 
 import torch
 
-from ..comm import (Handle, ShardSpec, all_to_all_bags, all_to_all_rows,
-                    all_to_all_values, exchange_sizes, plan_bags)
+from ..comm import (Handle, ShardSpec, all_to_all_bag_values, all_to_all_bags,
+                    all_to_all_rows, all_to_all_values, exchange_sizes,
+                    plan_bags)
 from ..dashboard import monitor
 from ..log import CHECK
 from ..updaters import AddOption
@@ -381,32 +387,8 @@ class MatrixTable(DenseTable):
         (``B == 0`` included) and the same ``weights is None`` (not checked).
         Float tables only. One lane group walks a bag serially, so a bag of
         tens of thousands of ids is slow (the limit of k_row_update)."""
-        self.flush()   # a deferred whole-table Add must land first
-        CHECK(self.dtype.is_floating_point,
-              f"pool_rows needs a float table, not {self.dtype}")
-        CHECK(mode in ("sum", "mean"),
-              f"pool_rows mode {mode!r} is not known ('sum' or 'mean')")
-        ids = torch.as_tensor(row_ids, dtype=torch.int64).reshape(-1)
-        if ids.is_cuda:
-            from ..dashboard import Dashboard
-            Dashboard.get("comm.keyed_d2h").count += 1
-        ids = ids.cpu()
-        offs = torch.as_tensor(offsets, dtype=torch.int64).cpu()
-        nnz = ids.numel()
-        CHECK(offs.dim() == 1 and offs.numel() >= 1 and int(offs[0]) == 0
-              and int(offs[-1]) == nnz and bool((offs.diff() >= 0).all()),
-              f"pool_rows offsets must be CSR [B+1]: 0 first, nnz={nnz} "
-              f"last, non-decreasing")
-        lo, hi = ids.aminmax() if nnz else (0, 0)
-        CHECK(int(lo) >= 0 and int(hi) < self.num_row,
-              f"pool_rows row_ids must lie in [0, {self.num_row})")
-        w = None
-        if weights is not None:
-            w = torch.as_tensor(weights)
-            CHECK(w.is_floating_point() and w.numel() == nnz,
-                  f"pool_rows weights must be float [{nnz}], got "
-                  f"{w.dtype} {tuple(w.shape)}")
-            w = w.reshape(-1).to(self.device, torch.float32)
+        ids, offs, w = self._check_bags("pool_rows", row_ids, offsets,
+                                        weights, mode)
         n_bags = offs.numel() - 1
         eng = self.engine
         with monitor("worker.pool_rows"):
@@ -478,6 +460,126 @@ class MatrixTable(DenseTable):
             out = torch.zeros(n_bags, self.num_col, dtype=self.dtype,
                               device=vals.device)
             return out.index_add_(0, bag_of, vals).to(self.wire)
+
+    def _check_bags(self, what: str, row_ids, offsets, weights, mode: str):
+        """The arguments ``pool_rows`` and ``add_pooled`` share, checked in
+        one place: flushes a deferred Add, then returns ``(ids, offsets)`` as
+        CPU int64 and the weights as fp32 on the table's device (or None)."""
+        self.flush()   # a deferred whole-table Add must land first
+        CHECK(self.dtype.is_floating_point,
+              f"{what} needs a float table, not {self.dtype}")
+        CHECK(mode in ("sum", "mean"),
+              f"{what} mode {mode!r} is not known ('sum' or 'mean')")
+        ids = torch.as_tensor(row_ids, dtype=torch.int64).reshape(-1)
+        if ids.is_cuda:
+            from ..dashboard import Dashboard
+            Dashboard.get("comm.keyed_d2h").count += 1
+        ids = ids.cpu()
+        offs = torch.as_tensor(offsets, dtype=torch.int64).cpu()
+        nnz = ids.numel()
+        CHECK(offs.dim() == 1 and offs.numel() >= 1 and int(offs[0]) == 0
+              and int(offs[-1]) == nnz and bool((offs.diff() >= 0).all()),
+              f"{what} offsets must be CSR [B+1]: 0 first, nnz={nnz} "
+              f"last, non-decreasing")
+        lo, hi = ids.aminmax() if nnz else (0, 0)
+        CHECK(int(lo) >= 0 and int(hi) < self.num_row,
+              f"{what} row_ids must lie in [0, {self.num_row})")
+        w = None
+        if weights is not None:
+            w = torch.as_tensor(weights)
+            CHECK(w.is_floating_point() and w.numel() == nnz,
+                  f"{what} weights must be float [{nnz}], got "
+                  f"{w.dtype} {tuple(w.shape)}")
+            w = w.reshape(-1).to(self.device, torch.float32)
+        return ids, offs, w
+
+    # ---- pooled Add: the embedding-bag backward, rebuilt where the rows live
+    def add_pooled(self, row_ids, offsets, bag_values, weights=None,
+                   mode: str = "sum",
+                   option: Optional[AddOption] = None) -> None:
+        """The Add that mirrors ``pool_rows``: ``bag_values`` is float
+        ``[B, num_col]``, one (gradient) row per bag, and the call is
+        ``add_rows(row_ids, vals, option)`` with ``vals[i] = w'_i *
+        bag_values[bag(i)]`` without those ``nnz`` rows ever existing.
+        ``row_ids``, ``offsets``, ``weights`` and ``mode`` are those of
+        ``pool_rows``, with the same checks; ``w'_i`` is ``weights[i]`` (1
+        without weights), in ``mean`` mode divided once, here, in fp32, by the
+        bag's full length.
+
+        One gradient row per bag and owner crosses the wire, against one per
+        id for ``add_rows``. Each owner sums, for every row it holds, the
+        contributions of the ids that name it, in caller order from ``+0.0``
+        (``acc + x``, weighted ``fma(w', x, acc)``; k_row_unpool on a float32
+        GPU shard, torch ops otherwise), and steps its updater once per
+        distinct row, for all seven updaters: rows not listed keep weights
+        and state, and a shard that receives no ids applies no update (Adam's
+        count does not advance there). No atomics are used, so the result is
+        repeatable bit for bit whatever the ``deterministic`` flag says. On a
+        bf16-wire table ``bag_values`` is rounded to bf16 once, here, on a
+        single rank too; the sums stay fp32. ``add_filter`` tables take it
+        unfiltered. ``option`` defaults as in ``add_rows``.
+
+        An Add: a deferred whole-table Add lands first, the sparse table's
+        freshness bitmap behaves as after ``add_rows``, and on the async
+        plane the call is tracked like ``add_rows``. On the sync plane it is
+        a collective: every rank calls it with its own bags (``B == 0``
+        included) and the same ``weights is None``. Float tables only. One
+        lane group walks a row's ids serially (the limit of k_row_update);
+        there is no max mode."""
+        ids, offs, w = self._check_bags("add_pooled", row_ids, offsets,
+                                        weights, mode)
+        n_bags = offs.numel() - 1
+        vals = torch.as_tensor(bag_values)
+        CHECK(vals.is_floating_point()
+              and vals.numel() == n_bags * self.num_col,
+              f"add_pooled bag_values must be float [{n_bags}, "
+              f"{self.num_col}], got {vals.dtype} {tuple(vals.shape)}")
+        vals = vals.to(self.device, self.wire).reshape(
+            n_bags, self.num_col).contiguous()
+        if mode == "mean":
+            lens = offs.diff()
+            div = torch.repeat_interleave(
+                lens.clamp(min=1).to(torch.float32), lens).to(self.device)
+            w = 1.0 / div if w is None else w / div
+        eng = self.engine
+        with monitor("worker.add_pooled"):
+            if eng is not None:
+                CHECK(self.zoo.is_worker,
+                      "add_pooled: ps_role=server ranks issue no Adds")
+                self._track(Handle(eng.pooled_add(
+                    self, ids, w, vals, plan_bags(ids, offs, self.spec),
+                    option)))
+            elif self.zoo.size > 1:
+                in_ids, in_offs, in_w, in_vals = all_to_all_bag_values(
+                    ids, w, vals, plan_bags(ids, offs, self.spec),
+                    self.device)
+                self._server_add_pooled(self._local_rows_of(in_ids), in_offs,
+                                        in_vals, in_w, option)
+            else:
+                # one owner holds every row: no plan and no gather, an id's
+                # gradient row is its bag's
+                self._server_add_pooled(ids.to(self.device),
+                                        offs.to(self.device), vals, w, option)
+
+    def _server_add_pooled(self, local_ids: torch.Tensor,
+                           offsets: torch.Tensor, vals2d: torch.Tensor,
+                           weights: Optional[torch.Tensor], option) -> None:
+        """The one server-side entry of add_pooled, for the local path and
+        both planes: ``vals2d`` ``[P, num_col]`` (wire dtype) holds one
+        gradient row per part, part p naming
+        ``local_ids[offsets[p]:offsets[p+1]]`` (int64 local row ids and CSR
+        offsets, fp32 weights or None, all on the table's device)."""
+        with self._shard_lock, monitor("server.update_pooled"):
+            nnz = local_ids.numel()
+            if not nnz:
+                return
+            # part of each id; output_size spares the host sync
+            src = torch.repeat_interleave(
+                torch.arange(offsets.numel() - 1, device=offsets.device),
+                offsets.diff(), output_size=nnz)
+            self.updater.update_pooled(local_ids, src, vals2d, weights,
+                                       option)
+            self._rows_added(local_ids)
 
     # ---- checkpoint (matrix_table.cpp:457-464) ----
     def store(self, path: str) -> None:

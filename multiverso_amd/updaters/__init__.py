@@ -127,7 +127,11 @@ class Updater:
     delta, *scalars, reverse=)``, ``X_copy_update(data, *state, delta, out,
     *scalars, reverse=)``, ``row_X_update(shard, *state, rows, vals,
     *scalars, perm)`` — so ``_hip_update`` and ``_hip_rows`` dispatch by
-    ``name``; the updaters whose entry points differ override them."""
+    ``name``; the updaters whose entry points differ override them.
+    ``update_pooled`` (the rows a pooled Add names) is a fourth form over the
+    same rule: ``unpool_X_update(shard, *state, rows, perm, src, vals,
+    weights, *scalars)`` exists for all seven names, so nothing overrides
+    it."""
 
     name: str
     whole_dtypes = (_F32, _F64)
@@ -249,6 +253,36 @@ class Updater:
                            assume_unique)
         else:
             self._torch_rows(w, state, local_ids, vals2d.to(w.dtype), scalars)
+
+    def update_pooled(self, local_ids: torch.Tensor, src: torch.Tensor,
+                      vals2d: torch.Tensor, weights: Optional[torch.Tensor],
+                      option: Optional[AddOption]) -> None:
+        """Pooled Add: ``update_rows(local_ids, vals, option)`` with
+        ``vals[i] = weights[i] * vals2d[src[i]]`` (1 without weights), where
+        ``vals2d`` holds one gradient row per bag part and ``src`` (int64,
+        below ``vals2d.size(0)``) names the part of each id. The keyed
+        semantics of ``_torch_rows``: contributions to one row are summed,
+        then the rule steps once per distinct row. On a float32 GPU shard
+        k_row_unpool sums each run of the stably sorted ids in registers, in
+        caller order from +0.0 (``acc + x``, weighted ``fma(w, x, acc)``), so
+        the expanded rows never exist, no atomics are used by any updater and
+        the ``deterministic`` flag changes nothing. Every other shard expands
+        and takes ``_torch_rows``. No ids is no update."""
+        if not local_ids.numel():
+            return
+        cols = vals2d.size(1)
+        state, scalars = self._resolve(option)
+        w, state = self.shard.view(-1, cols), [s.view(-1, cols) for s in state]
+        if self.shard.is_cuda and self.shard.dtype == _F32:
+            ids, perm = torch.sort(local_ids, stable=True)
+            getattr(_hip_ops(), f"unpool_{self.name}_update")(
+                w, *state, ids, perm, src, vals2d.contiguous(), weights,
+                *scalars)
+            return
+        vals = vals2d.to(w.dtype)[src]
+        if weights is not None:
+            vals = vals * weights.to(w.dtype).unsqueeze(1)
+        self._torch_rows(w, state, local_ids, vals, scalars)
 
     def access(self, out: torch.Tensor) -> None:
         """K7: shard copy-out (updater.cpp:32-36)."""
