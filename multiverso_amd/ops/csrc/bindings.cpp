@@ -676,6 +676,89 @@ void unpool_adam_update(torch::Tensor shard, torch::Tensor m, torch::Tensor v,
                         eps, &a, cur_stream());
 }
 
+// Row-wise AdaGrad: gsq holds one accumulator per row of the shard. The
+// launchers refuse a row wider than one lane group holds; that is an error
+// here, the updater asks the torch ops for such a table.
+void check_rowwise(const torch::Tensor& gsq, int64_t rows) {
+  check_f32(gsq, "g_sqr_row");
+  TORCH_CHECK(gsq.numel() == rows, "g_sqr_row must hold one value per row");
+}
+
+void check_rowwise_launched(int launched, int64_t cols) {
+  TORCH_CHECK(launched, "rowwise_adagrad: the kernels serve rows of up to "
+              "1024 columns (a multiple of 4, every pointer aligned) or 256 "
+              "columns, not ", cols);
+}
+
+void launch_rowwise_adagrad(const torch::Tensor& data,
+                            const torch::Tensor& gsq,
+                            const torch::Tensor& delta,
+                            const torch::Tensor* out, int64_t cols, double lr,
+                            double rho, double eps, bool reverse) {
+  int64_t n = check_same({{"data", data}});
+  TORCH_CHECK(cols >= 1 && n % cols == 0,
+              "data must hold whole rows of cols columns");
+  check_rowwise(gsq, n / cols);
+  int wire = wire_bit(delta, "delta", n, kWireDelta);
+  if (out) wire |= wire_bit(*out, "out", n, kWireOut);
+  check_rowwise_launched(
+      mv_launch_rowwise_adagrad(f32(data), f32(gsq), delta.data_ptr(),
+                                out ? out->data_ptr() : nullptr, wire,
+                                (float)lr, (float)rho, (float)eps, n / cols,
+                                cols, cur_stream(), reverse),
+      cols);
+}
+
+void rowwise_adagrad_update(torch::Tensor data, torch::Tensor gsq,
+                            torch::Tensor delta, int64_t cols, double lr,
+                            double rho, double eps, bool reverse) {
+  launch_rowwise_adagrad(data, gsq, delta, nullptr, cols, lr, rho, eps,
+                         reverse);
+}
+
+void rowwise_adagrad_copy_update(torch::Tensor data, torch::Tensor gsq,
+                                 torch::Tensor delta, torch::Tensor out,
+                                 int64_t cols, double lr, double rho,
+                                 double eps, bool reverse) {
+  launch_rowwise_adagrad(data, gsq, delta, &out, cols, lr, rho, eps, reverse);
+}
+
+// keyed: check_row_update's contract for rows, vals and perm; the list the
+// launcher takes has no src and no weights
+void row_rowwise_adagrad_update(torch::Tensor shard, torch::Tensor gsq,
+                                torch::Tensor rows, torch::Tensor vals,
+                                double lr, double rho, double eps,
+                                c10::optional<torch::Tensor> perm) {
+  int wire;
+  const int64_t* pp = check_row_update(shard, {}, rows, vals, perm, &wire);
+  check_rowwise(gsq, shard.size(0));
+  TORCH_CHECK(shard.size(1) >= 1 && rows.numel() <= INT32_MAX,
+              "a keyed Add takes fewer than 2^31 ids, of at least one column");
+  TORCH_CHECK(rows.numel() == 0 || shard.size(0) >= 1,
+              "ids into an empty shard");
+  MvUnpool a{vals.data_ptr(), wire, rows.data_ptr<int64_t>(), pp, nullptr,
+             nullptr, rows.numel(), shard.size(1)};
+  check_rowwise_launched(
+      mv_launch_unpool_rowwise_adagrad(f32(shard), f32(gsq), (float)lr,
+                                       (float)rho, (float)eps, &a,
+                                       cur_stream()),
+      a.cols);
+}
+
+void unpool_rowwise_adagrad_update(torch::Tensor shard, torch::Tensor gsq,
+                                   torch::Tensor rows, torch::Tensor perm,
+                                   torch::Tensor src, torch::Tensor vals,
+                                   OptTensor weights, double lr, double rho,
+                                   double eps) {
+  MvUnpool a = check_unpool(shard, {}, rows, perm, src, vals, weights);
+  check_rowwise(gsq, shard.size(0));
+  check_rowwise_launched(
+      mv_launch_unpool_rowwise_adagrad(f32(shard), f32(gsq), (float)lr,
+                                       (float)rho, (float)eps, &a,
+                                       cur_stream()),
+      a.cols);
+}
+
 void w2v_train(torch::Tensor in_emb, torch::Tensor out_emb,
                torch::Tensor in_gsq, torch::Tensor out_gsq,
                torch::Tensor in_idx, torch::Tensor in_off,
@@ -1302,6 +1385,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("perm"), py::arg("src"), py::arg("vals"), py::arg("weights"),
         py::arg("b1"), py::arg("b2"), py::arg("step"), py::arg("rbc2"),
         py::arg("decay"), py::arg("eps"));
+  m.def("rowwise_adagrad_update", &rowwise_adagrad_update,
+        "row-wise AdaGrad over the whole shard: one accumulator per row "
+        "(g_sqr_row [rows]), fed by the mean of the squared gradient over "
+        "the row's cols columns",
+        data, py::arg("g_sqr_row"), delta, py::arg("cols"), py::arg("lr"),
+        py::arg("rho"), py::arg("eps"), rev);
+  m.def("rowwise_adagrad_copy_update", &rowwise_adagrad_copy_update,
+        "fused row-wise AdaGrad Add+Get", data, py::arg("g_sqr_row"), delta,
+        out, py::arg("cols"), py::arg("lr"), py::arg("rho"), py::arg("eps"),
+        rev);
+  m.def("row_rowwise_adagrad_update", &row_rowwise_adagrad_update,
+        "keyed row-wise AdaGrad, same row/perm contract as "
+        "row_momentum_update",
+        py::arg("shard"), py::arg("g_sqr_row"), py::arg("rows"),
+        py::arg("vals"), py::arg("lr"), py::arg("rho"), py::arg("eps"),
+        py::arg("perm") = py::none());
+  m.def("unpool_rowwise_adagrad_update", &unpool_rowwise_adagrad_update,
+        "pooled row-wise AdaGrad, the contract of unpool_adagrad_update",
+        py::arg("shard"), py::arg("g_sqr_row"), py::arg("rows"),
+        py::arg("perm"), py::arg("src"), py::arg("vals"), py::arg("weights"),
+        py::arg("lr"), py::arg("rho"), py::arg("eps"));
   m.def("row_topk", &row_topk,
         "nearest rows: (scores [Q,k], global ids [Q,k]) of the k best shard "
         "rows per query, dot or cosine; None when one query exceeds the LDS "

@@ -3000,26 +3000,40 @@ extern "C" void mv_launch_row_pool(void* out, int wire, const float* shard,
 // walks a run serially.
 // ---------------------------------------------------------------------------
 
-// n >= 1 list positions; vcols counts V's per row
-template <class Op, int G, int VPL, class V, class D, bool WEIGHTED>
-__global__ __launch_bounds__(BLOCK) void k_row_unpool(
-    Op op, const D* __restrict__ vals, const int64_t* __restrict__ rows,
-    const int64_t* __restrict__ perm, const int64_t* __restrict__ src,
-    const float* __restrict__ wts, int n, int vcols) {
+// The columns of lane j of a group of G: vectors j, j + G, ... of the panel
+// that starts at vector `first`; a lane past the row's width is clamped to
+// the last vector and does not own it.
+template <int G, int VPL>
+static __device__ __forceinline__ void pool_cols(int (&col)[VPL],
+                                                 bool (&own)[VPL], int first,
+                                                 int j, int vcols) {
+#pragma unroll
+  for (int r = 0; r < VPL; ++r) {
+    int c = first + j + G * r;
+    own[r] = c < vcols;
+    col[r] = own[r] ? c : vcols - 1;
+  }
+}
+
+// The run walk, shared by k_row_unpool and k_row_unpool_rowwise: every run of
+// equal ids is summed into `acc` by one group, and done(head, run, acc) is
+// called by the whole wave once per round of heads; a group without a head
+// has head == false and run = rows[0], a valid row. NULLABLE (the keyed Add
+// of k_row_unpool_rowwise) lets src be null, position p naming row p of vals,
+// and then perm too (the identity). n >= 1 list positions. The pointers carry
+// the kernels' own __restrict__ and none here.
+template <int G, int VPL, class V, bool WEIGHTED, bool NULLABLE, class D,
+          class F>
+static __device__ __forceinline__ void unpool_walk(
+    const D* vals, const int64_t* rows, const int64_t* perm,
+    const int64_t* src, const float* wts, int n, int vcols,
+    const int (&col)[VPL], F done) {
   constexpr int U = pool_u(VPL), GPW = WAVE / G;
   constexpr uint64_t GMASK = G == WAVE ? ~0ull : (1ull << (G & 63)) - 1;
   const int lane = threadIdx.x & 63, j = lane & (G - 1), grp = lane / G;
   const int wave = __builtin_amdgcn_readfirstlane(
       (int)((blockIdx.x * BLOCK + threadIdx.x) >> 6));
   const int nwaves = gridDim.x * (BLOCK / WAVE);
-  int col[VPL];
-  bool own[VPL];
-#pragma unroll
-  for (int r = 0; r < VPL; ++r) {
-    int c = blockIdx.y * (G * VPL) + j + G * r;
-    own[r] = c < vcols;
-    col[r] = own[r] ? c : vcols - 1;
-  }
   for (int64_t base = (int64_t)wave * WAVE; base < n;
        base += (int64_t)nwaves * WAVE) {
     const int64_t pos = base + lane;
@@ -3047,8 +3061,14 @@ __global__ __launch_bounds__(BLOCK) void k_row_unpool(
         const int64_t at = k + j, atc = at < n ? at : n - 1;
         const bool live = walking && at < n && rows[atc] == run;
         const int left = __popcll((__ballot(live) >> (lane - j)) & GMASK);
-        const int64_t p = perm[atc];
-        const int64_t sid = src[p];
+        int64_t p, sid;
+        if constexpr (NULLABLE) {
+          p = perm ? perm[atc] : atc;
+          sid = src ? src[p] : p;
+        } else {
+          p = perm[atc];
+          sid = src[p];
+        }
         const float w = WEIGHTED ? wts[p] : 0.f;
         int cnt = left;
 #pragma unroll
@@ -3065,12 +3085,29 @@ __global__ __launch_bounds__(BLOCK) void k_row_unpool(
         walking = walking && left == G;
         if (!__any(walking)) break;
       }
-#pragma unroll
-      for (int r = 0; r < VPL; ++r)
-        if (head && own[r])
-          op.template step_at<V>(run * vcols + col[r], acc[r]);
+      done(head, run, acc);
     }
   }
+}
+
+// n >= 1 list positions; vcols counts V's per row
+template <class Op, int G, int VPL, class V, class D, bool WEIGHTED>
+__global__ __launch_bounds__(BLOCK) void k_row_unpool(
+    Op op, const D* __restrict__ vals, const int64_t* __restrict__ rows,
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ src,
+    const float* __restrict__ wts, int n, int vcols) {
+  int col[VPL];
+  bool own[VPL];
+  pool_cols<G, VPL>(col, own, blockIdx.y * (G * VPL),
+                    (threadIdx.x & 63) & (G - 1), vcols);
+  unpool_walk<G, VPL, V, WEIGHTED, false>(
+      vals, rows, perm, src, wts, n, vcols, col,
+      [&](bool head, int64_t run, V (&acc)[VPL]) {
+#pragma unroll
+        for (int r = 0; r < VPL; ++r)
+          if (head && own[r])
+            op.template step_at<V>(run * vcols + col[r], acc[r]);
+      });
 }
 
 // `vec` (every pointer of the op 16-byte aligned) with cols % 4 == 0 and
@@ -3166,6 +3203,255 @@ void mv_launch_unpool_adam(float* shard, float* m, float* v, double b1,
                                             step, rbc2, decay, eps),
                       vec, x, *a, s);
   });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Row-wise AdaGrad ("rowwise_adagrad", the optimiser behind an embedding
+// bag): ONE accumulator per row, fed by the mean of the squared gradient over
+// the row's columns.
+//   g     = delta / lr
+//   G[r] += (sum_c g[r,c]^2) / num_col
+//   w[r,c] -= (rho / sqrt(G[r] + eps)) * g[r,c]
+// No column can step before the whole row is reduced, so no Op::step_at fits:
+// the work split is the pooled kernels'. A row is served by a group of G lanes
+// (with_pool_shape: 4..64, 64 / G consecutive rows a wave), lane j holding
+// VPL column vectors V of the row's gradient in registers (pool_cols, one
+// panel). The whole row has to sit in one group, so there are no column
+// panels over gridDim.y: 64 * POOL_VPL_MAX vectors is the widest row, 1024
+// columns as v4f and 256 as float; the launchers return 0 for a wider one
+// and launch nothing.
+//
+// rowwise_step is the rule, on registers, and the only place it is written:
+// every lane sums the squares of its own columns with fma in the order
+// r = 0..VPL-1, x y z w, from +0.0 (a lane past the row's width holds a
+// clamped, valid column and leaves it out by a select), a __shfl_xor
+// butterfly with the masks 1, 2, .. G/2 leaves the same bits on all G lanes
+// (each level adds the same two numbers on both partners), lane 0 of the
+// group brings G[r] and the group gets it by broadcast. The three divides and
+// the square root are the correctly rounded ones: they run once per row (the
+// g = delta / lr once per element, where the pass has cycles to spare at
+// 12 B an element). The step itself is fma(-scale, g, w), kept off for
+// g == 0 so that a row without gradient keeps its bits. No LDS, no atomics,
+// no scratch.
+//
+// k_rowwise_elem<G, VPL, V, D, COPY, O>: the whole-shard Add and, with COPY,
+// the fused Add+Get. Rows go to groups by a grid-stride loop over wave slots
+// of 64 / G consecutive rows, so each of the streams stays coalesced; `rev`
+// walks the slots from the top down (the SWEEP note at launch_elem). The
+// delta is loaded once, non-temporal (ld); the shard plainly (ld_shard KEEP),
+// as in the other whole-shard passes; w and out are stored through st.
+//
+// k_row_unpool_rowwise<G, VPL, V, D, WEIGHTED>: the keyed and the pooled Add,
+// k_row_unpool's walk (unpool_walk) with rowwise_step on the run's summed
+// gradient as its epilogue. The keyed Add is the pooled one with src = the
+// identity and no weights: a null src (and then a null perm) says so.
+//
+// A row is computed from its summed gradient by the same geometry, the same
+// reduction order and the same formula in all four forms, so on one V they
+// agree bit for bit, whatever the grid or the rows that share the wave.
+// ---------------------------------------------------------------------------
+
+struct RowwiseScalars { float lr, rho, eps, ncol; };
+
+static __device__ __forceinline__ float rowwise_sq(float acc, float g) {
+  return __builtin_fmaf(g, g, acc);
+}
+static __device__ __forceinline__ float rowwise_sq(float acc, v4f g) {
+  acc = __builtin_fmaf(g.x, g.x, acc);
+  acc = __builtin_fmaf(g.y, g.y, acc);
+  acc = __builtin_fmaf(g.z, g.z, acc);
+  return __builtin_fmaf(g.w, g.w, acc);
+}
+
+static __device__ __forceinline__ float rowwise_move(float w, float g,
+                                                     float scale) {
+  return g == 0.f ? w : __builtin_fmaf(-scale, g, w);
+}
+static __device__ __forceinline__ v4f rowwise_move(v4f w, v4f g, float scale) {
+  v4f r;
+  r.x = rowwise_move(w.x, g.x, scale);
+  r.y = rowwise_move(w.y, g.y, scale);
+  r.z = rowwise_move(w.z, g.z, scale);
+  r.w = rowwise_move(w.w, g.w, scale);
+  return r;
+}
+
+// One row in the registers of its group: x is the (summed) delta, w the
+// weights, stepped in place; g_old is G[r] on lane 0 of the group (any value
+// elsewhere). Returns the new G[r], the same bits on every lane of the group.
+template <int G, int VPL, class V>
+static __device__ __forceinline__ float rowwise_step(
+    V (&w)[VPL], const V (&x)[VPL], const bool (&own)[VPL], float g_old,
+    const RowwiseScalars& k) {
+  V g[VPL];
+  float ss = 0.f;
+#pragma unroll
+  for (int r = 0; r < VPL; ++r) {
+    g[r] = x[r] / k.lr;
+    ss = own[r] ? rowwise_sq(ss, g[r]) : ss;
+  }
+#pragma unroll
+  for (int m = 1; m < G; m <<= 1) ss += __shfl_xor(ss, m, WAVE);
+  const float g_new = pool_bcast<G>(g_old, 0) + ss / k.ncol;
+  const float scale = k.rho / __builtin_elementwise_sqrt(g_new + k.eps);
+#pragma unroll
+  for (int r = 0; r < VPL; ++r) w[r] = rowwise_move(w[r], g[r], scale);
+  return g_new;
+}
+
+// R >= 1 rows of vcols <= G * VPL vectors V
+template <int G, int VPL, class V, class D, bool COPY, class O>
+__global__ __launch_bounds__(BLOCK) void k_rowwise_elem(
+    float* __restrict__ data, float* __restrict__ gsq,
+    const D* __restrict__ delta, O* __restrict__ out, RowwiseScalars k,
+    int64_t R, int vcols, int rev) {
+  constexpr int GPW = WAVE / G;
+  const int lane = threadIdx.x & 63, j = lane & (G - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(
+      (int)((blockIdx.x * BLOCK + threadIdx.x) >> 6));
+  const int nwaves = gridDim.x * (BLOCK / WAVE);
+  int col[VPL];
+  bool own[VPL];
+  pool_cols<G, VPL>(col, own, 0, j, vcols);
+  const int64_t slots = (R + GPW - 1) / GPW;
+  for (int64_t s = wave; s < slots; s += nwaves) {
+    const int64_t row = (rev ? slots - 1 - s : s) * GPW + lane / G;
+    const bool live = row < R;
+    const int64_t rc = live ? row : R - 1, at = rc * vcols;
+    V x[VPL], w[VPL];
+#pragma unroll
+    for (int r = 0; r < VPL; ++r) x[r] = ld<V>(delta, at + col[r]);
+#pragma unroll
+    for (int r = 0; r < VPL; ++r) w[r] = ld_shard<V, true>(data, at + col[r]);
+    const float g_old = j == 0 ? gsq[rc] : 0.f;
+    const float g_new = rowwise_step<G, VPL>(w, x, own, g_old, k);
+    if (live && j == 0) gsq[rc] = g_new;
+#pragma unroll
+    for (int r = 0; r < VPL; ++r)
+      if (live && own[r]) {
+        st(data, at + col[r], w[r]);
+        if (COPY) st(out, at + col[r], w[r]);
+      }
+  }
+}
+
+// n >= 1 list positions; vcols <= G * VPL counts V's per row
+template <int G, int VPL, class V, class D, bool WEIGHTED>
+__global__ __launch_bounds__(BLOCK) void k_row_unpool_rowwise(
+    float* __restrict__ data, float* __restrict__ gsq, RowwiseScalars k,
+    const D* __restrict__ vals, const int64_t* __restrict__ rows,
+    const int64_t* __restrict__ perm, const int64_t* __restrict__ src,
+    const float* __restrict__ wts, int n, int vcols) {
+  const int j = (threadIdx.x & 63) & (G - 1);
+  int col[VPL];
+  bool own[VPL];
+  pool_cols<G, VPL>(col, own, 0, j, vcols);
+  unpool_walk<G, VPL, V, WEIGHTED, true>(
+      vals, rows, perm, src, wts, n, vcols, col,
+      [&](bool head, int64_t run, V (&acc)[VPL]) {
+        const int64_t at = run * vcols;
+        V w[VPL];
+#pragma unroll
+        for (int r = 0; r < VPL; ++r) w[r] = ld<V>(data, at + col[r]);
+        const float g_old = j == 0 ? gsq[run] : 0.f;
+        const float g_new = rowwise_step<G, VPL>(w, acc, own, g_old, k);
+        if (head && j == 0) gsq[run] = g_new;
+#pragma unroll
+        for (int r = 0; r < VPL; ++r)
+          if (head && own[r]) st(data, at + col[r], w[r]);
+      });
+}
+
+// The widest row one group holds, in vectors
+#define ROWWISE_VCOLS_MAX (WAVE * POOL_VPL_MAX)
+
+// V = v4f needs cols % 4 == 0, the shard 16-byte aligned and the vector
+// alignment of the delta and of out; everything else takes the scalar form
+// of the same source. Returns 0, having launched nothing, for a row wider
+// than ROWWISE_VCOLS_MAX vectors.
+template <class D, class O>
+static int launch_rowwise_elem(float* data, float* gsq, const D* delta, O* out,
+                               const RowwiseScalars& k, int64_t R,
+                               int64_t cols, int rev, hipStream_t s) {
+  constexpr bool narrow_out = std::is_same<O, bf16>::value;
+  bool vec = cols % 4 == 0 && aligned16(data) && vals_vec_ok(delta) &&
+             (narrow_out ? ((uintptr_t)out & 7) == 0 : aligned16(out));
+  int64_t vcols = vec ? cols / 4 : cols;
+  if (vcols > ROWWISE_VCOLS_MAX) return 0;
+  if (!R) return 1;
+  with_pool_shape(vcols, [&](auto g, auto v) {
+    constexpr int G = decltype(g)::value, VPL = decltype(v)::value;
+    int64_t per_block = BLOCK / G;
+    int grid = grid_for_cap((R + per_block - 1) / per_block * BLOCK,
+                            POOL_GRID);
+    auto go = [&](auto vtag) {
+      using V = decltype(vtag);
+      if (out)
+        k_rowwise_elem<G, VPL, V, D, true><<<grid, BLOCK, 0, s>>>(
+            data, gsq, delta, out, k, R, (int)vcols, rev);
+      else
+        k_rowwise_elem<G, VPL, V, D, false><<<grid, BLOCK, 0, s>>>(
+            data, gsq, delta, out, k, R, (int)vcols, rev);
+    };
+    if (vec) go(v4f{});
+    else go(0.f);
+  });
+  return 1;
+}
+
+template <class D>
+static int launch_row_unpool_rowwise(float* data, float* gsq,
+                                     const RowwiseScalars& k, const D* vals,
+                                     const MvUnpool& a, hipStream_t s) {
+  bool vec = a.cols % 4 == 0 && aligned16(data) && vals_vec_ok(vals);
+  int64_t vcols = vec ? a.cols / 4 : a.cols;
+  if (vcols > ROWWISE_VCOLS_MAX) return 0;
+  if (!a.n) return 1;
+  with_pool_shape(vcols, [&](auto g, auto v) {
+    constexpr int G = decltype(g)::value, VPL = decltype(v)::value;
+    int grid = grid_for_cap(a.n, POOL_GRID);
+    auto go = [&](auto vtag) {
+      using V = decltype(vtag);
+      if (a.wts)
+        k_row_unpool_rowwise<G, VPL, V, D, true><<<grid, BLOCK, 0, s>>>(
+            data, gsq, k, vals, a.rows, a.perm, a.src, a.wts, (int)a.n,
+            (int)vcols);
+      else
+        k_row_unpool_rowwise<G, VPL, V, D, false><<<grid, BLOCK, 0, s>>>(
+            data, gsq, k, vals, a.rows, a.perm, a.src, a.wts, (int)a.n,
+            (int)vcols);
+    };
+    if (vec) go(v4f{});
+    else go(0.f);
+  });
+  return 1;
+}
+
+extern "C" {
+
+int mv_launch_rowwise_adagrad(float* data, float* gsq, const void* delta,
+                              void* out, int wire, float lr, float rho,
+                              float eps, int64_t rows, int64_t cols,
+                              hipStream_t s, int rev) {
+  int ok = 0;
+  RowwiseScalars k{lr, rho, eps, (float)cols};
+  with_wire(wire, delta, out, [&](auto* d, auto* o) {
+    ok = launch_rowwise_elem(data, gsq, d, o, k, rows, cols, rev, s);
+  });
+  return ok;
+}
+
+int mv_launch_unpool_rowwise_adagrad(float* shard, float* gsq, float lr,
+                                     float rho, float eps, const MvUnpool* a,
+                                     hipStream_t s) {
+  int ok = 0;
+  RowwiseScalars k{lr, rho, eps, (float)a->cols};
+  with_unpool_vals(*a, [&](auto* x) {
+    ok = launch_row_unpool_rowwise(shard, gsq, k, x, *a, s);
+  });
+  return ok;
 }
 
 }  // extern "C"

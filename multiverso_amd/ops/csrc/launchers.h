@@ -12,7 +12,9 @@
 // fp32, or bf16 when wire has WIRE_DELTA; rows [n] are the sorted local ids,
 // perm [n] the caller's position of each; src [n] (the row of vals, below P)
 // and wts [n] (or null) are in caller order. n and P are below 2^31; n == 0
-// launches nothing.
+// launches nothing. The row-wise AdaGrad launcher alone also takes a null src
+// (the keyed Add: position p names row p of vals, so vals has n rows) and
+// then a null perm (the identity: rows is in caller order).
 struct MvUnpool {
   const void* vals;
   int wire;
@@ -125,6 +127,17 @@ void mv_launch_unpool_dcasgda(float*, float*, float*, float, float, float,
 void mv_launch_unpool_adam(float*, float*, float*, double, double, double,
                            double, double, double, const MvUnpool*,
                            hipStream_t);
+// row-wise AdaGrad (k_rowwise_elem, k_row_unpool_rowwise): gsq holds ONE
+// accumulator per row. Whole shard: (data, gsq [rows], delta, out-or-null,
+// wire, lr, rho, eps, rows, cols, stream, reverse); keyed and pooled: the
+// arguments of mv_launch_unpool_adagrad. Both return 0, having launched
+// nothing, when a row is wider than one lane group holds: 1024 columns with
+// cols % 4 == 0 and aligned pointers, 256 otherwise.
+int mv_launch_rowwise_adagrad(float*, float*, const void*, void*, int, float,
+                              float, float, int64_t, int64_t, hipStream_t,
+                              int);
+int mv_launch_unpool_rowwise_adagrad(float*, float*, float, float, float,
+                                     const MvUnpool*, hipStream_t);
 // word2vec: (in_emb, out_emb, in_gsq, out_gsq, in_idx, in_off, ...,
 // groups, dim, use_adagrad, use_atomic)
 void mv_launch_w2v(float*, float*, float*, float*, const int64_t*, const int*,

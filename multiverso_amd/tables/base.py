@@ -184,8 +184,11 @@ class Table:
                 out_flat.copy_(src.cpu() if out_flat.device.type == "cpu"
                                else src.to(out_flat.device))
 
-    def _make_updater(self, shard: torch.Tensor) -> None:
-        self.updater = create_updater(self.updater_type, shard)
+    def _make_updater(self, shard: torch.Tensor,
+                      num_col: Optional[int] = None) -> None:
+        """``num_col``: the row width of a matrix table's shard (an array
+        table has none), for the updater that keeps state per row."""
+        self.updater = create_updater(self.updater_type, shard, num_col)
 
     # ---- async bookkeeping ----
     def _track(self, handle: Handle) -> Handle:

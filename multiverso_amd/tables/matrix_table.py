@@ -136,7 +136,7 @@ class MatrixTable(DenseTable):
             full = torch.rand(num_row, num_col, generator=g) * (hi - lo) + lo
             self.shard.copy_(full[self.row_offset:
                                   self.row_offset + self.local_rows])
-        self._make_updater(self.shard.view(-1))
+        self._make_updater(self.shard.view(-1), num_col)
         self._init_dense(num_row * num_col, num_col, (num_row, num_col))
 
     # ---- row-keyed ops (matrix_table.cpp:59-147, K5/K6) ----

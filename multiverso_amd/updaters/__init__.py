@@ -19,12 +19,18 @@ Capability parity with the reference updater family (selected by the
            from a submodule absent in the snapshot; math from Zheng et
            al., ICML 2017) with per-worker backup rows.
 
-One updater goes beyond the reference's set:
+Two updaters go beyond the reference's set:
 
 - adam:    Adam / AdamW as in ``torch.optim`` (``SparseAdam`` for keyed
            Adds): first and second moment per element, ONE update count
            per shard on the host, bias corrections passed to the kernel as
            scalars (``AdamUpdater``). float32 and float64 tables.
+- rowwise_adagrad: adagrad with ONE accumulator per row, fed by the mean of
+           the squared gradient over the row's columns
+           (``RowwiseAdaGradUpdater``): the embedding-table optimiser, its
+           state 1/num_col of adagrad's. Matrix tables only; its HIP kernels
+           hold a row in one lane group and serve num_col <= 1024 (256 when
+           num_col is no multiple of 4), wider tables run the torch ops.
 
 ``AddOption`` keeps the reference's 20-byte wire envelope
 (include/multiverso/updater/updater.h:10-70) for C-API parity; adam's
@@ -130,8 +136,9 @@ class Updater:
     ``name``; the updaters whose entry points differ override them.
     ``update_pooled`` (the rows a pooled Add names) is a fourth form over the
     same rule: ``unpool_X_update(shard, *state, rows, perm, src, vals,
-    weights, *scalars)`` exists for all seven names, so nothing overrides
-    it."""
+    weights, *scalars)`` exists for all eight names, so nothing overrides
+    it. ``_hip_serves`` and ``_state_rows`` are the two hooks of an updater
+    whose state is not one value per element."""
 
     name: str
     whole_dtypes = (_F32, _F64)
@@ -159,6 +166,18 @@ class Updater:
     def _resolve(self, option: Optional[AddOption]):
         """(state tensors, scalars) of one update under ``option``."""
         raise NotImplementedError
+
+    def _hip_serves(self, *payload: torch.Tensor) -> bool:
+        """Whether the HIP kernels of a covered shard dtype take this launch,
+        given the delta, vals or Get buffer it would hand them. They do for
+        every updater whose kernels step element by element; one that needs a
+        whole row in a lane group has a widest row, and sends wider tables to
+        ``torch_step``."""
+        return True
+
+    def _state_rows(self, state, cols: int):
+        """The state tensors as the keyed forms index them, by row."""
+        return [s.view(-1, cols) for s in state]
 
     def _hip_update(self, state, delta: torch.Tensor,
                     out: Optional[torch.Tensor], scalars) -> None:
@@ -198,7 +217,8 @@ class Updater:
 
     def update(self, delta: torch.Tensor, option: Optional[AddOption]) -> None:
         state, scalars = self._resolve(option)
-        if self.shard.is_cuda and self.shard.dtype in self.whole_dtypes:
+        if (self.shard.is_cuda and self.shard.dtype in self.whole_dtypes
+                and self._hip_serves(delta)):
             self._hip_update(state, delta, None, scalars)
         else:
             self.torch_step(self.shard, *state, _widened(delta), scalars)
@@ -210,7 +230,8 @@ class Updater:
         stream the updated shard into ``out`` in the same pass — saves
         the Get's shard re-read. Every updater has a fused HIP kernel;
         the fallback composes update + copy."""
-        if self.shard.is_cuda and self.shard.dtype in self.fused_dtypes:
+        if (self.shard.is_cuda and self.shard.dtype in self.fused_dtypes
+                and self._hip_serves(delta, out)):
             state, scalars = self._resolve(option)
             self._hip_update(state, delta, out, scalars)
         else:
@@ -246,10 +267,12 @@ class Updater:
             assume_unique = True
         cols = vals2d.size(1)
         state, scalars = self._resolve(option)
-        w, state = self.shard.view(-1, cols), [s.view(-1, cols) for s in state]
-        if self.shard.is_cuda and self.shard.dtype in self.keyed_dtypes:
+        w, state = self.shard.view(-1, cols), self._state_rows(state, cols)
+        vals2d = vals2d.contiguous()
+        if (self.shard.is_cuda and self.shard.dtype in self.keyed_dtypes
+                and self._hip_serves(vals2d)):
             # a bf16-wire payload reaches the kernel as it is
-            self._hip_rows(w, state, local_ids, vals2d.contiguous(), scalars,
+            self._hip_rows(w, state, local_ids, vals2d, scalars,
                            assume_unique)
         else:
             self._torch_rows(w, state, local_ids, vals2d.to(w.dtype), scalars)
@@ -272,12 +295,13 @@ class Updater:
             return
         cols = vals2d.size(1)
         state, scalars = self._resolve(option)
-        w, state = self.shard.view(-1, cols), [s.view(-1, cols) for s in state]
-        if self.shard.is_cuda and self.shard.dtype == _F32:
+        w, state = self.shard.view(-1, cols), self._state_rows(state, cols)
+        vals2d = vals2d.contiguous()
+        if (self.shard.is_cuda and self.shard.dtype == _F32
+                and self._hip_serves(vals2d)):
             ids, perm = torch.sort(local_ids, stable=True)
             getattr(_hip_ops(), f"unpool_{self.name}_update")(
-                w, *state, ids, perm, src, vals2d.contiguous(), weights,
-                *scalars)
+                w, *state, ids, perm, src, vals2d, weights, *scalars)
             return
         vals = vals2d.to(w.dtype)[src]
         if weights is not None:
@@ -506,6 +530,83 @@ class AdamUpdater(Updater):
         return (self.exp_avg, self.exp_avg_sq), self.next_scalars(option)
 
 
+class RowwiseAdaGradUpdater(Updater):
+    """Row-wise AdaGrad ("rowwise_adagrad"), the optimiser embedding tables
+    run behind ``pool_rows`` / ``add_pooled``: AdaGrad with ONE accumulator
+    per row, fed by the mean of the squared gradient over the row's columns.
+
+        g     = delta / lr
+        G[r] += (sum_c g[r,c]^2) / num_col
+        w[r,c] -= (rho / sqrt(G[r] + eps)) * g[r,c]
+
+    The project's AdaGrad convention: the delta arrives pre-scaled by
+    ``AddOption.learning_rate``, ``AddOption.rho`` is the step size and
+    ``EPS`` is ``AdaGradUpdater.EPS``. The state ``g_sqr_row`` holds one
+    value of the shard's dtype per ROW (``[local_rows]``: 4 MB where
+    "adagrad" keeps 800 MB on a float32 1M x 200 table), zero at
+    construction. Matrix tables only: an array has no rows.
+
+    A column cannot step before its whole row is reduced, so the HIP kernels
+    (k_rowwise_elem, k_row_unpool_rowwise; float32 shards) hold a row in the
+    registers of one lane group. That sets a widest row: ``num_col <= 1024``
+    when ``num_col % 4 == 0`` and the payload is vector-aligned, ``num_col
+    <= 256`` otherwise. A wider table takes ``torch_step`` / ``_torch_rows``
+    on the GPU: correct, and slower. The keyed and pooled forms sum duplicate
+    ids in caller order without atomics, so they are repeatable."""
+
+    name = "rowwise_adagrad"
+    EPS = AdaGradUpdater.EPS
+    whole_dtypes = (_F32,)
+
+    def __init__(self, shard: torch.Tensor,
+                 num_col: Optional[int] = None) -> None:
+        if num_col is None:
+            raise TypeError("updater_type 'rowwise_adagrad' keeps one "
+                            "accumulator per row and an array has no rows: "
+                            "use a MatrixTable, or 'adagrad'")
+        if shard.dtype not in (_F32, _F64):
+            raise TypeError(f"updater_type 'rowwise_adagrad' needs a float32 "
+                            f"or float64 table, got {shard.dtype} (integer "
+                            f"tables are add-only: use 'default')")
+        super().__init__(shard)
+        self.num_col = int(num_col)
+        self.g_sqr_row = torch.zeros(shard.numel() // self.num_col,
+                                     dtype=shard.dtype, device=shard.device)
+
+    def _resolve(self, option):
+        opt = option or AddOption()
+        return (self.g_sqr_row,), (float(opt.learning_rate), float(opt.rho),
+                                   self.EPS)
+
+    def torch_step(self, w, gsq, g, scalars) -> None:
+        """The rule in torch ops, in place on w and gsq: w and g hold whole
+        rows (flat or [rows, num_col]), gsq one value for each."""
+        lr, rho, eps = scalars
+        w, g = w.view(-1, self.num_col), g.view(-1, self.num_col) / lr
+        gsq.add_((g * g).sum(1) / self.num_col)
+        w.sub_((rho / torch.sqrt(gsq + eps)).unsqueeze(1) * g)
+
+    def _hip_serves(self, *payload: torch.Tensor) -> bool:
+        # what launch_rowwise_elem / launch_row_unpool_rowwise ask of the
+        # v4f form: 16-byte fp32 vectors, 8-byte bf16 ones
+        vec = self.num_col % 4 == 0 and all(
+            t.data_ptr() % (4 * t.element_size()) == 0 for t in payload)
+        return self.num_col <= (1024 if vec else 256)
+
+    def _state_rows(self, state, cols: int):
+        return list(state)   # already one value per row
+
+    def _hip_update(self, state, delta, out, scalars) -> None:
+        hip, rev = _hip_ops(), self._sweep()
+        if out is None:
+            hip.rowwise_adagrad_update(self.shard, *state, delta,
+                                       self.num_col, *scalars, reverse=rev)
+        else:
+            hip.rowwise_adagrad_copy_update(self.shard, *state, delta, out,
+                                            self.num_col, *scalars,
+                                            reverse=rev)
+
+
 _REGISTRY: Dict[str, Type[Updater]] = {
     "default": DefaultUpdater,
     "sgd": SGDUpdater,
@@ -514,14 +615,20 @@ _REGISTRY: Dict[str, Type[Updater]] = {
     "dcasgd": DCASGDUpdater,
     "dcasgda": DCASGDAUpdater,
     "adam": AdamUpdater,
+    "rowwise_adagrad": RowwiseAdaGradUpdater,
 }
 
 
-def create_updater(name: str, shard: torch.Tensor) -> Updater:
-    """Factory keyed by the ``updater_type`` flag (updater.cpp:46-57)."""
+def create_updater(name: str, shard: torch.Tensor,
+                   num_col: Optional[int] = None) -> Updater:
+    """Factory keyed by the ``updater_type`` flag (updater.cpp:46-57).
+    ``num_col`` is the row width of a matrix table's shard, None for an
+    array; only the row-wise updater looks at it."""
     try:
         cls = _REGISTRY[name]
     except KeyError:
         raise ValueError(f"unknown updater_type '{name}' "
                          f"(have {sorted(_REGISTRY)})") from None
+    if cls is RowwiseAdaGradUpdater:
+        return cls(shard, num_col)
     return cls(shard)
